@@ -12,10 +12,13 @@ the hot path over one batch of synthetic camera views on every rank (config C4 o
     (soft_mask*G2).sum() (kaolin_amd.metrics.render.weighted_sum: one fused pass each way; "torch_loss_variant" = the same
     loss as two torch dots) down to the shared vertices -> ONE all-reduce of the vertex gradient (N > 1).
 Views are sharded over ranks (weak scaling: 8 views per GPU), no collective on the data path.  Inputs are
-resident in HBM when the timed region starts.  The same run also times chamfer_distance fwd+bwd at
-100k x 100k (config C3, one batch item per GPU) and reports it under "chamfer".
+resident in HBM when the timed region starts.
 
-Rank 0 prints ONE JSON line.  "roofline" describes the kernel with the largest share of the DIB-R step, timed
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up steps, times K steps and prints the headline (`value`,
+`ms_per_step`, ...) -- nothing else.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
+With `--full` the same run also times chamfer_distance fwd+bwd at 100k x 100k (config C3, one batch item per GPU, under
+"chamfer"), the step's variants, the other scenes, graph replay, the contract operators and C5, and reports the following.
+"roofline" describes the kernel with the largest share of the DIB-R step, timed
 live with HIP events on the launch stream inside the timed region (libkaolin_amd's kamd_profile_* hooks: the DIB-R kernels
 are launched through hipExtLaunchKernelGGL, whose two events take the dispatch's own begin and end timestamps -- the interval
 rocprofv3's kernel trace reports; the table of every kernel comes from a separate, fully instrumented pass of the same step
@@ -31,6 +34,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -72,6 +76,12 @@ def parse():
                          'to 8-11, image-sized triangles, geometry leaving the image); the default run also times the knot scene and reports '
                          'it under "scene_variants"')
     ap.add_argument('--no-scene-variants', action='store_true', help='skip the timing of the other scene')
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything besides the headline too: the per-kernel table and roofline, the step\'s variants, the other '
+                         'scenes, graph replay, contract operators, chamfer, C5 and the CPU baseline (the --no-* options above pick among '
+                         'them).  Without it a run sets up, warms up, times the K steps and prints the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last timed step computed on rank 0 as DIR/<name>.npy (see dump_outputs)')
     ap.add_argument('--dump-vertex-grad', default=None, metavar='FILE',
                     help='tests: after the timed steps run one more step and save rank 0\'s (all-reduced) vertex gradient with torch.save')
     ap.add_argument('--look-at', type=float, nargs=3, default=[0., 0., 0.],
@@ -125,6 +135,34 @@ def pick_dominant(kernels):
     top = kernels[ranked[0]]['share_of_instrumented_step']
     near = [k for k in ranked if kernels[k]['share_of_instrumented_step'] >= 0.95 * top]
     return next((k for k in near if k not in OVERLAPPED), ranked[0])
+
+
+DUMP_PIXELS = 1 << 20      # --dump-outputs: pixels kept of the image-sized outputs (a fixed, seeded sample of them beyond that)
+DUMP_VERTICES = 1 << 20    # and rows kept of the vertex gradient
+
+
+def sample_rows(t, n, seed):
+    """`t` as it is if it has at most `n` rows (first dimension), else a fixed, seeded sample of `n` of them in index order."""
+    if t.shape[0] <= n:
+        return t
+    idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(dirname, features, soft_mask, face_idx, vertex_grad):
+    """--dump-outputs: what one step hands its caller, as DIR/<name>.npy.  The rasterizer's `features` (V, H, W, D), `soft_mask`
+    (V, H, W) and `face_idx` (V, H, W) as one row per pixel, the same seeded sample of DUMP_PIXELS pixels for all three (float32;
+    face_idx as float64, which holds it exactly), and the vertex gradient (float32, at most DUMP_VERTICES rows).  At D = 3 that is
+    at most 36 MB.  Returns {name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    P = face_idx.numel()
+    arrays = {'features': sample_rows(features.detach().reshape(P, -1), DUMP_PIXELS, 0).float(),
+              'soft_mask': sample_rows(soft_mask.detach().reshape(P), DUMP_PIXELS, 0).float(),
+              'face_idx': sample_rows(face_idx.reshape(P), DUMP_PIXELS, 0).double(),
+              'vertex_grad': sample_rows(vertex_grad.detach(), DUMP_VERTICES, 1).float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), t.cpu().numpy())
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def cpu_reference_extras(n_points=100000, slice_rows=4096, raster_res=32, sphere_frequency=50, seed=0):
@@ -292,6 +330,7 @@ def relaunch_as_ranks(n):
 def main():
     args = parse()
     if args.quick:
+        args.full = True   # (the instrumented headline of --full: kernel table and roofline, none of its other measurements)
         args.no_cpu_baseline = args.no_chamfer = args.no_c5 = args.no_contract_ops = True
     if args.cpu_extras_only:
         print(json.dumps(cpu_reference_extras(args.chamfer_points, sphere_frequency=args.sphere_frequency)))
@@ -340,7 +379,8 @@ def main():
     verts, faces, F, rot, trans, feats3, reducer = (scene[k] for k in ('verts', 'faces', 'F', 'rot', 'trans', 'feats3', 'reducer'))
     feats3_grad = feats3.clone().requires_grad_()          # variant: learnable per-face features (a texture atlas per view)
 
-    def make_step(sc, features, tutorial_loss=False, torch_loss=False):
+    def make_step(sc, features, tutorial_loss=False, torch_loss=False, keep=None):
+        """`keep` (a dict): every step leaves its rasterizer outputs in it until write_outputs has written them (--dump-outputs)."""
         verts_, faces_, rot_, trans_, reducer_ = sc['verts'], sc['faces'], sc['rot'], sc['trans'], sc['reducer']
 
         def step():
@@ -361,9 +401,14 @@ def main():
                 loss = kal.metrics.render.weighted_sum(feat, G1, soft, G2)
             loss.backward()
             reducer_.wait()
+            if keep is not None and not keep.get('written'):
+                # (detached: a kept output with its grad_fn keeps the step's autograd graph -- and the vertices' AccumulateGrad node,
+                # bound to the stream it was made on -- alive into the next step, which breaks the graph capture of --full)
+                keep.update(features=feat.detach(), soft_mask=soft.detach(), face_idx=face_idx)
             return face_idx
         return step
-    dibr_step = make_step(scene, feats3)
+    last_outputs = {}
+    dibr_step = make_step(scene, feats3, keep=last_outputs if args.dump_outputs else None)
     dibr_step_tutorial = make_step(scene, feats3, tutorial_loss=True)
     dibr_step_torch_loss = make_step(scene, feats3, torch_loss=True)
     dibr_step_feature_grad = make_step(scene, feats3_grad)
@@ -508,6 +553,61 @@ def main():
                                                             camera_rot=sc['rot'], camera_trans=sc['trans'])
         return float((normals[..., 2] >= 0).float().sum()) / V
 
+    workload = (f'{"C4" if args.scene == "sphere" else "C4 shape, scene " + args.scene}: dibr_rasterization fwd+bwd, {V} views/GPU at {H}x{W} of a {F}-triangle '
+                f'{"geodesic sphere" if args.scene == "sphere" else "non-convex knot scene (kaolin_amd.utils.testing.knot_mesh)" + (", faces in random order" if args.scene == "knot_shuffled" else "")} '
+                f'(shared vertices), D=3 static face features (uv + mask channel; gradient w.r.t. the vertices only), '
+                f'knum=30, sigmainv=7000, boxlen=0.02, loss = sum(features*G1) + sum(soft_mask*G2) (fused weighted_sum), '
+                f'prepare_vertices + vertex-gradient all-reduce (posted from the autograd hook) inside the step')
+
+    def distributed_info(posted_per_step):
+        return {'initialized': D.is_distributed(),
+                'backend': torch.distributed.get_backend() if D.is_distributed() else None,
+                'collectives_posted_per_step': round(posted_per_step, 3),
+                'visible_gpus': torch.cuda.device_count(),
+                'ranks_per_gpu': max(1, -(-world // max(torch.cuda.device_count(), 1)))}
+
+    def write_outputs():
+        """--dump-outputs, straight after the headline's timed steps: what the last of them computed"""
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_outputs['features'], last_outputs['soft_mask'], last_outputs['face_idx'], verts.grad)
+        last_outputs.clear()
+        last_outputs['written'] = True     # (the steps after this one keep nothing)
+
+    def write_vertex_grad():
+        if args.dump_vertex_grad:
+            dibr_step()
+            torch.cuda.synchronize()
+            if rank == 0:
+                torch.save(verts.grad.detach().cpu(), args.dump_vertex_grad)
+
+    def close_group():
+        if D.is_distributed():
+            D.barrier()     # rank 0 may still run the --full extras and print the line: the group goes down only when every rank is done
+            torch.distributed.destroy_process_group()
+
+    if not args.full:
+        # ---------------- a plain run: W warm-up steps, the K timed steps, the outputs, the line -- nothing else
+        posted0 = reducer.posted
+        dt = timed(dibr_step, args.steps, args.warmup)
+        posted_per_step = (reducer.posted - posted0) / (args.steps + args.warmup)
+        enqueue_ms = timed.enqueue_ms
+        write_outputs()
+        write_vertex_grad()
+        if rank == 0:
+            print(json.dumps({
+                'metric': 'Mpixels/s DIB-R fwd+bwd @1024^2', 'value': round(world * V * H * W * args.steps / dt / 1e6, 2), 'unit': 'Mpixels/s',
+                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 4),
+                'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+                'host_enqueue_ms_per_step': round(enqueue_ms, 4),
+                'config': {'workload': workload, 'views_per_gpu': V, 'global_views': V * world, 'height': H, 'width': W, 'faces': F,
+                           'scene': args.scene, 'parallelism': f'views sharded {world}-way', 'look_at': list(args.look_at)},
+                'distributed': distributed_info(posted_per_step),
+                'full': False,
+                'notes': {'full': 'a plain run times the headline step only: the per-kernel table, roofline, variants, other scenes, '
+                                  'chamfer, C5 and the CPU baseline are measured with --full'}}))
+        close_group()
+        return
+
     # ---------------- DIB-R.  Timing a launch costs stream time (a profiled dispatch, or two event records), and timing every
     # kernel also keeps the operator's two concurrent launches (side stream) on one stream.  So: (1) an instrumented
     # pass outside the timed region gives the per-kernel table and names the dominant kernel; (2) the timed region runs
@@ -526,6 +626,7 @@ def main():
     posted0 = reducer.posted
     dt = timed(dibr_step, args.steps, max(2, args.warmup))   # (untimed steps in THIS mode: its event pool is created on first use)
     reducer_posted_per_step = (reducer.posted - posted0) / (args.steps + max(2, args.warmup))
+    write_outputs()
     dibr_enqueue_ms = timed.enqueue_ms
     dibr_enqueue_idle_ms = host_enqueue_idle_ms(dibr_step)
     lib.kamd_profile_enable(0)
@@ -535,11 +636,7 @@ def main():
     mpix = world * V * H * W * args.steps / dt / 1e6
 
     step_stats = per_step_ms(dibr_step, max(args.steps, 20))
-    if args.dump_vertex_grad:
-        dibr_step()
-        torch.cuda.synchronize()
-        if rank == 0:
-            torch.save(verts.grad.detach().cpu(), args.dump_vertex_grad)
+    write_vertex_grad()
     feature_grad = tutorial = torch_loss = None
     if not args.quick:
         # variant with gradients w.r.t. the face features as well (raster_backward adds its feature-gradient atomics)
@@ -1052,21 +1149,13 @@ def main():
             'roofline': None if roofline is None else dict(roofline, same_run=headline_scalars),
             'cpu_baseline': None if cpu is None else {k: v for k, v in cpu.items() if k not in ('other_paths', 'sample')} | {'sample': cpu['sample']},
             **{'also_' + k: v for k, v in headline_scalars.items()},
-            'config': {'workload': f'{"C4" if args.scene == "sphere" else "C4 shape, scene " + args.scene}: dibr_rasterization fwd+bwd, {V} views/GPU at {H}x{W} of a {F}-triangle '
-                                   f'{"geodesic sphere" if args.scene == "sphere" else "non-convex knot scene (kaolin_amd.utils.testing.knot_mesh)" + (", faces in random order" if args.scene == "knot_shuffled" else "")} '
-                                   f'(shared vertices), D=3 static face features (uv + mask channel; gradient w.r.t. the vertices only), '
-                                   f'knum=30, sigmainv=7000, boxlen=0.02, loss = sum(features*G1) + sum(soft_mask*G2) (fused weighted_sum), '
-                                   f'prepare_vertices + vertex-gradient all-reduce (posted from the autograd hook) inside the step',
+            'config': {'workload': workload,
                        'views_per_gpu': V, 'global_views': V * world, 'height': H, 'width': W, 'faces': F,
                        'scene': args.scene, 'front_faces_per_view': round(Fv, 1),
                        'covered_pixel_fraction': round(covered, 4), 'covered_tile_pixel_fraction': round(p_cov / (H * W), 4),
                        'parallelism': f'views sharded {world}-way', 'look_at': list(args.look_at)},
             'per_step_ms': step_stats, 'kernels': kernels, 'step_roofline': step_roofline,
-            'distributed': {'initialized': D.is_distributed(),
-                            'backend': torch.distributed.get_backend() if D.is_distributed() else None,
-                            'collectives_posted_per_step': round(reducer_posted_per_step, 3),
-                            'visible_gpus': torch.cuda.device_count(),
-                            'ranks_per_gpu': max(1, -(-world // max(torch.cuda.device_count(), 1)))},
+            'distributed': distributed_info(reducer_posted_per_step),
             'chamfer': chamfer, 'c5': c5,
             'feature_grad_variant': feature_grad, 'tutorial_loss_variant': tutorial, 'torch_loss_variant': torch_loss,
             'work_units_per_view': headline_units, 'scene_variants': scene_variants,
@@ -1081,9 +1170,7 @@ def main():
                                               f'order they need cost the difference); the timed region times the roofline kernel only'),
         }
         print(json.dumps(out))
-    if D.is_distributed():
-        D.barrier()     # rank 0 still runs the C5 extras and prints the line: the group goes down only when every rank is done
-        torch.distributed.destroy_process_group()
+    close_group()
 
 
 if __name__ == '__main__':

@@ -74,3 +74,32 @@ def test_knot_shuffled_scene_is_a_permutation_of_the_knot():
     assert torch.equal(key(f0), key(f1))
     _, f2 = T.scene_mesh('knot_shuffled')
     assert torch.equal(f1, f2)  # (a fixed seed: every run renders the same order)
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays under 64 MB in all, the same seeded pixel sample for the three image-sized
+    outputs (rows of one pixel each) and from run to run; outputs at most the sample's size are written whole."""
+    import numpy as np
+    import torch
+    V, H, W, D, N = 5, 512, 512, 3, 30000
+    g = torch.Generator().manual_seed(3)
+    feats = torch.rand((V, H, W, D), generator=g)
+    soft = torch.randperm(V * H * W, generator=g).float().reshape(V, H, W)   # (distinct values: they name their pixel)
+    face_idx = torch.randint(-1, 50000, (V, H, W), generator=g)
+    vgrad = torch.rand((N, 3), generator=g, dtype=torch.float64)
+    shapes = bench.dump_outputs(str(tmp_path / 'a'), feats, soft, face_idx, vgrad)
+    bench.dump_outputs(str(tmp_path / 'b'), feats, soft, face_idx, vgrad)
+    n = bench.DUMP_PIXELS
+    assert V * H * W > n and shapes == {'features': [n, D], 'soft_mask': [n], 'face_idx': [n], 'vertex_grad': [N, 3]}
+    a = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in shapes}
+    b = {k: np.load(tmp_path / 'b' / f'{k}.npy') for k in shapes}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert {k: x.dtype for k, x in a.items()} == {'features': np.float32, 'soft_mask': np.float32, 'face_idx': np.float64,
+                                                  'vertex_grad': np.float32}
+    assert all(np.array_equal(a[k], b[k]) for k in shapes)
+    # the three image outputs are sampled at the same pixels, in index order: soft_mask's values name them
+    pix = np.argsort(soft.reshape(-1).numpy())[a['soft_mask'].astype(np.int64)]
+    assert np.all(np.diff(pix) > 0)
+    assert np.array_equal(a['features'], feats.reshape(-1, D).numpy()[pix])
+    assert np.array_equal(a['face_idx'], face_idx.reshape(-1).numpy()[pix].astype(np.float64))
+    assert np.array_equal(a['vertex_grad'], vgrad.float().numpy())

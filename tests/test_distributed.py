@@ -336,7 +336,7 @@ def test_bench_under_torchrun_one_rank_rccl(tmp_path):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
            '--res', '256', '--sphere-frequency', '16', '--views-per-gpu', '4', '--chamfer-points', '20000', '--no-c5',
-           '--no-cpu-baseline']
+           '--no-cpu-baseline', '--full']
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{')][-1])

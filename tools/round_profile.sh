@@ -35,10 +35,10 @@ fi
 # THIS library's (the committed line cited the table of an earlier commit)
 if [ -s $out/traffic.json ]; then cp $out/traffic.json $repo/profiles/traffic.json; fi
 cd $repo
-timeout 600 python bench.py 2> $out/bench.err | tail -1 > $out/bench.json
+timeout 600 python bench.py --full 2> $out/bench.err | tail -1 > $out/bench.json
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
 cd /tmp && export TMPDIR=/tmp
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python $repo/bench.py --no-cpu-baseline --no-contract-ops --no-scene-variants 2> $out/prof.err | tail -1 > $out/bench_under_rocprof.json
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python $repo/bench.py --full --no-cpu-baseline --no-contract-ops --no-scene-variants 2> $out/prof.err | tail -1 > $out/bench_under_rocprof.json
 find $out/prof -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats.csv \;
 rm -rf $out/prof
 cd $repo; ls -la $out; cat $out/bench.json | cut -c1-400
