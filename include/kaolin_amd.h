@@ -436,6 +436,34 @@ int kamd_dibr_rasterization_backward_f64(void* stream, int B, int H, int W, int 
                                          uint32_t* work, const double* img, const double* feat,
                                          double multiplier, float eps, float sigmainv,
                                          double* g_img, double* g_feat);
+/* The backward of the linear loss sum(features * w_feat) + sum(soft_mask *    */
+/* w_soft) of the forward's two outputs, through the forward: the arguments of  */
+/* ..._backward with (grad_loss, w_feat, w_soft) in place of the two output      */
+/* gradients.  grad_loss: the loss' gradient, ONE device scalar (read on the     */
+/* device: no host sync); w_feat (B,H,W,D) and w_soft (B,H,W): the weights, laid */
+/* out as the outputs; w_soft may be NULL (no soft-mask term).  The output       */
+/* gradients grad_loss * w are formed where the kernels read them: the same      */
+/* values ..._backward would consume from materialised gradients.                */
+int kamd_dibr_weighted_sum_backward_f32(void* stream, int B, int H, int W, int F, int D, int K,
+                                        const float* grad_loss, const float* w_feat,
+                                        const float* w_soft,
+                                        const int64_t* face_idx, const float* weights,
+                                        const float* soft_mask, const int32_t* hit_pair,
+                                        const float* hit_prob,
+                                        const int32_t* hit_rec, const int32_t* item_count,
+                                        uint32_t* work, const float* img, const float* feat,
+                                        double multiplier, float eps, float sigmainv,
+                                        float* g_img, float* g_feat);
+int kamd_dibr_weighted_sum_backward_f64(void* stream, int B, int H, int W, int F, int D, int K,
+                                        const double* grad_loss, const double* w_feat,
+                                        const double* w_soft,
+                                        const int64_t* face_idx, const double* weights,
+                                        const double* soft_mask, const int32_t* hit_pair,
+                                        const double* hit_prob,
+                                        const int32_t* hit_rec, const int32_t* item_count,
+                                        uint32_t* work, const double* img, const double* feat,
+                                        double multiplier, float eps, float sigmainv,
+                                        double* g_img, double* g_feat);
 
 /* ------------------------------------------------------------------------- */
 /* render.mesh.prepare_vertices, fused (the reference is     */

@@ -505,6 +505,42 @@ def dibr_rasterization_backward_fused(grad_features, grad_soft_mask, face_idx, o
     return g_img, g_feat
 
 
+def dibr_weighted_sum_backward_fused(grad_loss, w_features, w_soft_mask, face_idx, output_weights, soft_mask, hits,
+                                     face_vertices_image, face_features, sigmainv, knum, multiplier, eps,
+                                     need_feature_grad=True, zeroed_grad_image=None):
+    """:func:`dibr_rasterization_backward_fused` for the linear loss ``sum(features * w_features) + sum(soft_mask * w_soft_mask)``
+    of the forward's outputs, given its gradient ``grad_loss`` (a scalar tensor on the device): the kernels read the weights and
+    form ``grad_loss * w`` themselves where they use a gradient -- no output-sized gradient is written.  ``w_soft_mask`` may
+    be None (no soft-mask term).  -> (grad_face_vertices_image, grad_face_features or None)"""
+    fn = 'dibr_weighted_sum_backward_fused'
+    batch_size, height, width, feat_dim = w_features.shape
+    num_faces = face_vertices_image.size(1)
+    dtype, device = face_vertices_image.dtype, face_vertices_image.device
+    tensors = (w_features, face_idx, output_weights, soft_mask, face_vertices_image, face_features) + \
+        ((w_soft_mask,) if w_soft_mask is not None else ())
+    if not (face_vertices_image.is_cuda and all(t.device == device and t.is_contiguous() for t in tensors) and
+            all(t.dtype == dtype for t in tensors if t is not face_idx) and
+            (w_soft_mask is None or w_soft_mask.shape == (batch_size, height, width)) and
+            face_idx.shape == (batch_size, height, width) and output_weights.shape == (batch_size, height, width, 3) and
+            face_vertices_image.shape == (batch_size, num_faces, 3, 2) and
+            face_features.shape == (batch_size, num_faces, 3, feat_dim)):
+        raise RuntimeError(f'{fn}: the weights must be contiguous tensors of the outputs\' shapes, dtype and device')
+    sfx = _lib.dtype_suffix(dtype, fn)
+    lib = _lib.load()
+    with _lib.on_device(device):
+        g = grad_loss.to(dtype).reshape(1).contiguous()
+        g_img = zeroed_grad_image if zeroed_grad_image is not None else torch.zeros_like(face_vertices_image)
+        g_feat = torch.zeros_like(face_features) if need_feature_grad else None
+        st = getattr(lib, f'kamd_dibr_weighted_sum_backward_{sfx}')(
+            _lib.stream_ptr(device), batch_size, height, width, num_faces, feat_dim, int(knum),
+            _lib.ptr(g), _lib.ptr(w_features), _lib.ptr(w_soft_mask), _lib.ptr(face_idx), _lib.ptr(output_weights),
+            _lib.ptr(soft_mask), _lib.ptr(hits[0]), _lib.ptr(hits[1]), _lib.ptr(hits[2]), _lib.ptr(hits[3]),
+            _lib.ptr(hits[4]), _lib.ptr(face_vertices_image), _lib.ptr(face_features),
+            float(multiplier), float(eps), float(sigmainv), _lib.ptr(g_img), _lib.ptr(g_feat))
+    _lib.check(st, fn)
+    return g_img, g_feat
+
+
 def _storage_key(t):
     """What identifies the DATA a tensor shows: a fresh tensor object over the same storage (`faces[:]`, `.view(...)`, a property
     that re-wraps) has a new id() but the same key.  Sound only while a cache entry pins a tensor of that storage (the address

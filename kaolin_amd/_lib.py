@@ -87,6 +87,8 @@ for _t in ('f32', 'f64'):
         _i, [_vp, _i, _i, _i, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _dbl, _f, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_dibr_rasterization_backward_{_t}'] = (
         _i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 12 + [_dbl, _f, _f, _vp, _vp])
+    SIGNATURES[f'kamd_dibr_weighted_sum_backward_{_t}'] = (
+        _i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 13 + [_dbl, _f, _f, _vp, _vp])
     SIGNATURES[f'kamd_mask_iou_forward_{_t}'] = (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_mask_iou_backward_{_t}'] = (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_weighted_sum2_forward_{_t}'] = (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp])

@@ -432,13 +432,20 @@ int soft_mask_forward_launch(hipStream_t st, int B, int H, int W, int F, int K, 
 template <typename T>
 int soft_mask_backward_list_launch(hipStream_t st, int B, int H, int W, int F, int K, const T* grad, const T* soft_mask,
                                    const HitList2<T>& list, const unsigned int* work, const T* img, double img_scale,
-                                   float sigmainv, float multiplier, T* g_img, unsigned int* bigwork = nullptr) {
+                                   float sigmainv, float multiplier, T* g_img, unsigned int* bigwork = nullptr,
+                                   const T* grad_scale = nullptr /* non-null: `grad` holds weights, the gradient is *grad_scale * grad */) {
   if ((long long)B * H * W <= 0 || F <= 0) return 0;
   {
     // persistent workgroups over the rounds of 256 hits (their number is known on the device only)
     static const int per_cu = kamd_env_int("KAMD_SOFT_BWD_PER_CU", 16);
-    KAMD_LAUNCH_TIMED(kamd::K_SOFT_BACKWARD_LIST, soft_mask_backward_flat_kernel<T>, dim3(KAMD_NUM_CU * per_cu), dim3(256), 0, st, H, W, F,
-                      flat_view_magic(F), grad, soft_mask, list, img, (T)img_scale, sigmainv, multiplier, 1.0 / (double)multiplier, g_img, bigwork);
+    if (grad_scale != nullptr)
+      KAMD_LAUNCH_TIMED(kamd::K_SOFT_BACKWARD_LIST, (soft_mask_backward_flat_kernel<T, true>), dim3(KAMD_NUM_CU * per_cu), dim3(256), 0, st, H, W, F,
+                        flat_view_magic(F), grad, soft_mask, list, img, (T)img_scale, sigmainv, multiplier, 1.0 / (double)multiplier, g_img, bigwork,
+                        grad_scale);
+    else
+      KAMD_LAUNCH_TIMED(kamd::K_SOFT_BACKWARD_LIST, (soft_mask_backward_flat_kernel<T, false>), dim3(KAMD_NUM_CU * per_cu), dim3(256), 0, st, H, W, F,
+                        flat_view_magic(F), grad, soft_mask, list, img, (T)img_scale, sigmainv, multiplier, 1.0 / (double)multiplier, g_img, bigwork,
+                        grad_scale);
   }
   KAMD_RETURN_LAST_ERROR();
 }
@@ -561,11 +568,15 @@ int side_stream(SideStream** out) {
   return 0;
 }
 
+// grad_scale non-null (kamd_dibr_weighted_sum_backward_*): grad_feat / grad_soft are the weights W1 / W2 of the loss
+// sum(features * W1) + sum(soft_mask * W2) and the incoming gradients *grad_scale * W1 / W2 are formed inside the two kernels,
+// where they are read -- nothing image-sized is written.  grad_soft may then be null (no soft-mask term): its launch is skipped
 template <typename T>
 int dibr_backward_fused(hipStream_t st, int B, int H, int W, int F, int D, int K, const T* grad_feat, const T* grad_soft,
                         const int64_t* face_idx, const T* weights, const T* soft_mask, const HitList2<T>& list,
                         unsigned int* work, const T* img, const T* feat, double multiplier, float eps, float sigmainv,
-                        T* g_img, T* g_feat) {
+                        T* g_img, T* g_feat, const T* grad_scale = nullptr) {
+  const bool soft_term = grad_scale == nullptr || grad_soft != nullptr;
   // The two backward kernels are independent and used to overlap on a side stream (61 || 73 us: ~110 together).  Since the
   // rasterizer's backward leaves empty tiles at once (48 us) the fork / join events and the contention cost more than the
   // overlap saves: one stream, step -9 us (KAMD_BWD_SIDE_STREAM=1 restores the side stream, for A/B runs; while the
@@ -582,16 +593,20 @@ int dibr_backward_fused(hipStream_t st, int B, int H, int W, int F, int D, int K
     // first launch, folded into g_img and cleared by the second; only when the second one is the list form)
     const bool list_form = cov_list && tile_cov != nullptr;
     unsigned int* bigwork = list_form && kamd_env_int("KAMD_BWD_BIG_SIDE", 1) == 1 ? work + tl::WORK_BIGHASH_WORD : nullptr;
-    KAMD_CHECK(soft_mask_backward_list_launch<T>(st, B, H, W, F, K, grad_soft, soft_mask, list, work, img, multiplier, sigmainv,
-                                                 (float)multiplier, g_img, bigwork));
+    if (soft_term)
+      KAMD_CHECK(soft_mask_backward_list_launch<T>(st, B, H, W, F, K, grad_soft, soft_mask, list, work, img, multiplier, sigmainv,
+                                                   (float)multiplier, g_img, bigwork, grad_scale));
     if (list_form)
       return kamd::raster_backward_draw_list<T>(st, B, H, W, F, D, grad_feat, face_idx, weights, img, feat, eps, g_img, g_feat,
                                                 work + tl::WORK_COV_WORD, work + tl::work_covlist_offset_words(B, H, W),
                                                 tl::cov_shard_cap((size_t)B, (size_t)tl::pass_geom(H, W, tl::R_TILE).ntiles),
-                                                work + tl::WORK_MAGIC_WORD, bigwork);
+                                                work + tl::WORK_MAGIC_WORD, bigwork, grad_scale);
     return kamd::raster_backward_draw<T>(st, B, H, W, F, D, grad_feat, face_idx, weights, img, feat, eps, g_img, g_feat, tile_cov,
-                                         row_centre);
+                                         row_centre, grad_scale);
   }
+  if (!soft_term)
+    return kamd::raster_backward_draw<T>(st, B, H, W, F, D, grad_feat, face_idx, weights, img, feat, eps, g_img, g_feat, tile_cov,
+                                         row_centre, grad_scale);
   std::lock_guard<std::mutex> lk(g_side_mu);
   SideStream* ss;
   KAMD_CHECK(side_stream(&ss));
@@ -600,12 +615,12 @@ int dibr_backward_fused(hipStream_t st, int B, int H, int W, int F, int D, int K
   KAMD_CHECK(hipStreamWaitEvent(side, ss->fork, 0));
   // after the fork every exit goes through the join: the caller may free the buffers as soon as this returns
   int rc = soft_mask_backward_list_launch<T>(side, B, H, W, F, K, grad_soft, soft_mask, list, work, img, multiplier, sigmainv,
-                                             (float)multiplier, g_img);
+                                             (float)multiplier, g_img, nullptr, grad_scale);
   int rc2 = (int)hipEventRecord(ss->join, side);
   if (rc == 0) rc = rc2;
   if (rc == 0)
     rc = kamd::raster_backward_draw<T>(st, B, H, W, F, D, grad_feat, face_idx, weights, img, feat, eps, g_img, g_feat, tile_cov,
-                                       row_centre);
+                                       row_centre, grad_scale);
   rc2 = (int)hipStreamWaitEvent(st, ss->join, 0);
   return rc != 0 ? rc : rc2;
 }
@@ -732,6 +747,16 @@ size_t kamd_dibr_rasterization_workspace(int B, int H, int W, int F, int K, int 
     HitList2<T> l{(int2*)hit_pair, (T*)hit_prob, (uint2*)hit_rec, (int*)item_count, (unsigned int*)work + FLAT_COUNT_WORD, flat_shard_cap_of(B, H, W, K)};                               \
     return dibr_backward_fused<T>((hipStream_t)stream, B, H, W, F, D, K, grad_feat, grad_soft, face_idx, weights,     \
                                   soft_mask, l, work, img, feat, multiplier, eps, sigmainv, g_img, g_feat);           \
+  }                                                                                                                   \
+  int kamd_dibr_weighted_sum_backward_##SFX(                                                                          \
+      void* stream, int B, int H, int W, int F, int D, int K, const T* grad_loss, const T* w_feat, const T* w_soft,   \
+      const int64_t* face_idx, const T* weights, const T* soft_mask, const int32_t* hit_pair, const T* hit_prob,      \
+      const int32_t* hit_rec, const int32_t* item_count, uint32_t* work, const T* img, const T* feat,                \
+      double multiplier, float eps, float sigmainv, T* g_img, T* g_feat) {                                            \
+    if (grad_loss == nullptr || w_feat == nullptr) return (int)hipErrorInvalidValue;                                  \
+    HitList2<T> l{(int2*)hit_pair, (T*)hit_prob, (uint2*)hit_rec, (int*)item_count, (unsigned int*)work + FLAT_COUNT_WORD, flat_shard_cap_of(B, H, W, K)};                               \
+    return dibr_backward_fused<T>((hipStream_t)stream, B, H, W, F, D, K, w_feat, w_soft, face_idx, weights,           \
+                                  soft_mask, l, work, img, feat, multiplier, eps, sigmainv, g_img, g_feat, grad_loss); \
   }
 KAMD_SOFT_ENTRY(f32, float)
 KAMD_SOFT_ENTRY(f64, double)

@@ -88,11 +88,13 @@ PHASE_TABLE(g_phase_rbwd)
 
 // one 16 x 16-pixel tile of image b: workgroup = the tile, wavefront = 16 x 4 pixels.  Called by every thread of the workgroup
 // (barriers inside); may be called for one tile after another (its LDS tables are re-initialised behind a barrier).
-template <typename T, int DT, bool GF>
+// SW ("scaled weights", weighted_sum's backward fused in): `grad` holds the loss weights W and the incoming gradient of pixel p is
+// gs * W[p] -- the product weighted_sum2_backward_kernel would have stored, formed where it is read (covered pixels only).
+template <typename T, int DT, bool GF, bool SW>
 __device__ __forceinline__ void raster_backward_tile(
     int b, int tile, int tiles_x, int H, int W, int F, int D, const T* __restrict__ grad, const int64_t* __restrict__ face_idx,
     const T* __restrict__ weights, const T* __restrict__ img, const T* __restrict__ feat, float eps,
-    T* __restrict__ g_img, T* __restrict__ g_feat) {
+    T* __restrict__ g_img, T* __restrict__ g_feat, T gs) {
   constexpr int NV = (DT > 0 && GF) ? 6 + 3 * DT : 6;
   constexpr bool STAGED = DT > 0;                              // run totals go to global memory through per-wavefront staging rows
   __shared__ int s_runf[STAGED ? 4 : 1][STAGED ? 64 : 1];      // the runs' faces ...
@@ -118,7 +120,7 @@ __device__ __forceinline__ void raster_backward_tile(
     const T* ff = feat + tf * 3 * D;
     const int nd = DT > 0 ? DT : D;
     for (int d = 0; d < nd; ++d) {
-      const T gd = g[d];
+      const T gd = SW ? gs * g[d] : g[d];
       const T c0 = ff[d], c1 = ff[D + d], c2 = ff[2 * D + d];
       const T dldI = gd / (k3 * k3);
 #pragma unroll
@@ -224,12 +226,12 @@ __device__ __forceinline__ void raster_backward_tile(
   PHASE_FLUSH(g_phase_rbwd);
 }
 
-template <typename T, int DT, bool GF>
+template <typename T, int DT, bool GF, bool SW>
 __global__ __launch_bounds__(256) void raster_backward_kernel(
     int B, int H, int W, int F, int D, const T* __restrict__ grad, const int64_t* __restrict__ face_idx,
     const T* __restrict__ weights, const T* __restrict__ img, const T* __restrict__ feat, float eps,
     T* __restrict__ g_img, T* __restrict__ g_feat, const unsigned char* __restrict__ tile_cov,
-    const unsigned int* __restrict__ row_span) {
+    const unsigned int* __restrict__ row_span, const T* __restrict__ grad_scale /* SW: the loss' incoming gradient, one scalar */) {
   // (fused dibr_rasterization: the forward pass noted which tiles hold a covered pixel -- 85 % of C4's do not, and
   // finding that out from face_idx costs a 2-KB read and a barrier per workgroup: 24 of this kernel's 60 us)
   const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
@@ -242,20 +244,21 @@ __global__ __launch_bounds__(256) void raster_backward_kernel(
   const int tile = blockIdx.x % (tiles_x * tiles_y), b = blockIdx.x / (tiles_x * tiles_y);
 #endif
   if (tile_cov != nullptr && tile_cov[(size_t)b * (tiles_x * tiles_y) + tile] == 0) return;
-  raster_backward_tile<T, DT, GF>(b, tile, tiles_x, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat);
+  const T gs = SW ? *grad_scale : (T)1;
+  raster_backward_tile<T, DT, GF, SW>(b, tile, tiles_x, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat, gs);
 }
 
 // The fused operator's backward: the forward's tile kernel left the list of the tiles that hold a covered pixel (15 % of C4's
 // tiles; tl::queue_items_reached, COV_SHARDS shards) -- a persistent grid walks it, workgroup w taking entries w, w + grid, ...
 // The one-workgroup-per-tile launch above spent ~45 % of its wavefront time on the 26k workgroups whose only act is to
 // find their tile's coverage byte clear (index arithmetic, two dependent loads, exit): 49 -> xx us at C4.
-template <typename T, int DT, bool GF>
+template <typename T, int DT, bool GF, bool SW>
 __global__ __launch_bounds__(256) void raster_backward_list_kernel(
     int B, int H, int W, int F, int D, const T* __restrict__ grad, const int64_t* __restrict__ face_idx,
     const T* __restrict__ weights, const T* __restrict__ img, const T* __restrict__ feat, float eps,
     T* __restrict__ g_img, T* __restrict__ g_feat, const unsigned int* __restrict__ cov_counts,
     const unsigned int* __restrict__ cov_list, unsigned int cov_cap, int grouped, const unsigned int* __restrict__ magic_word,
-    unsigned int magic, unsigned int* __restrict__ bigwork) {
+    unsigned int magic, unsigned int* __restrict__ bigwork, const T* __restrict__ grad_scale /* SW only */) {
   __shared__ unsigned int s_end[tl::COV_SHARDS];  // inclusive prefix of the shards' entry counts
   const int tiles_x = (W + 15) / 16, ntiles = tiles_x * ((H + 15) / 16);
   const int lane = threadIdx.x & 63;
@@ -283,11 +286,12 @@ __global__ __launch_bounds__(256) void raster_backward_list_kernel(
   // The list is trusted only with the forward's signature in the header (tl::WORK_MAGIC_WORD: a work buffer of another
   // operator / build / shape would otherwise be read as tile indices); without it every tile is visited -- each wavefront
   // finds out from face_idx whether it has anything to do, as the one-workgroup-per-tile launch does.  (Uniform: a scalar load.)
+  const T gs = SW ? *grad_scale : (T)1;  // (uniform: a scalar load)
   if (magic_word == nullptr || *magic_word != magic) {
     const unsigned int all = (unsigned int)B * (unsigned int)ntiles;
     for (unsigned int id = blockIdx.x; id < all; id += gridDim.x) {
       const int b = (int)(id / (unsigned int)ntiles), tile = (int)(id - (unsigned int)b * (unsigned int)ntiles);
-      raster_backward_tile<T, DT, GF>(b, tile, tiles_x, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat);
+      raster_backward_tile<T, DT, GF, SW>(b, tile, tiles_x, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat, gs);
     }
     return;
   }
@@ -313,7 +317,7 @@ __global__ __launch_bounds__(256) void raster_backward_list_kernel(
     const unsigned int id = cov_list[(size_t)sh * cov_cap + (i - start)];
     const int b = (int)(id / (unsigned int)ntiles), tile = (int)(id - (unsigned int)b * (unsigned int)ntiles);
     if (b >= B) continue;  // (never with a list the forward wrote: belt and braces behind the signature check)
-    raster_backward_tile<T, DT, GF>(b, tile, tiles_x, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat);
+    raster_backward_tile<T, DT, GF, SW>(b, tile, tiles_x, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat, gs);
   }
 }
 
@@ -371,17 +375,24 @@ int rasterize_forward_fused_launch(hipStream_t st, int B, int H, int W, int F, i
 template <typename T>
 int rasterize_backward_launch(hipStream_t st, int B, int H, int W, int F, int D, const T* grad, const int64_t* face_idx,
                               const T* weights, const T* img, const T* feat, float eps, T* g_img, T* g_feat,
-                              const unsigned char* tile_cov = nullptr, const unsigned int* row_span = nullptr) {
+                              const unsigned char* tile_cov = nullptr, const unsigned int* row_span = nullptr,
+                              const T* grad_scale = nullptr /* non-null: `grad` holds weights, the gradient is *grad_scale * grad */) {
   const long long total = (long long)B * H * W;
   if (total <= 0 || F <= 0) return 0;
   const dim3 grid((unsigned)(B * ((W + 15) / 16) * ((H + 15) / 16)));
-#define KAMD_RB(DT)                                                                                                   \
+#define KAMD_RB_GF(DT, SW)                                                                                            \
   if (g_feat != nullptr)                                                                                              \
-    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_kernel<T, DT, true>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx,  \
-                      weights, img, feat, eps, g_img, g_feat, tile_cov, row_span);                                    \
+    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_kernel<T, DT, true, SW>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx,  \
+                      weights, img, feat, eps, g_img, g_feat, tile_cov, row_span, grad_scale);                        \
   else                                                                                                                \
-    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_kernel<T, DT, false>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx, \
-                      weights, img, feat, eps, g_img, g_feat, tile_cov, row_span)
+    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_kernel<T, DT, false, SW>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx, \
+                      weights, img, feat, eps, g_img, g_feat, tile_cov, row_span, grad_scale)
+#define KAMD_RB(DT)                                                                                                   \
+  if (grad_scale != nullptr) {                                                                                        \
+    KAMD_RB_GF(DT, true);                                                                                             \
+  } else {                                                                                                            \
+    KAMD_RB_GF(DT, false);                                                                                            \
+  }
   switch (D) {
     case 1: KAMD_RB(1); break;
     case 2: KAMD_RB(2); break;
@@ -390,6 +401,7 @@ int rasterize_backward_launch(hipStream_t st, int B, int H, int W, int F, int D,
     default: KAMD_RB(0); break;
   }
 #undef KAMD_RB
+#undef KAMD_RB_GF
   return (int)hipGetLastError();
 }
 
@@ -398,20 +410,26 @@ template <typename T>
 int rasterize_backward_list_launch(hipStream_t st, int B, int H, int W, int F, int D, const T* grad, const int64_t* face_idx,
                                    const T* weights, const T* img, const T* feat, float eps, T* g_img, T* g_feat,
                                    const unsigned int* cov_counts, const unsigned int* cov_list, unsigned int cov_cap,
-                                   const unsigned int* magic_word, unsigned int* bigwork) {
+                                   const unsigned int* magic_word, unsigned int* bigwork, const T* grad_scale) {
   const long long n_groups = (long long)B * ((W + 15) / 16) * ((H + 15) / 16);
   const unsigned int magic = tl::work_magic(B, H, W);
   if (n_groups <= 0 || F <= 0) return 0;
   static const int per_cu = kamd_env_int("KAMD_RBWD_PER_CU", 16);
   static const int grouped = kamd_env_int("KAMD_RBWD_GROUPED", 1) == 1 ? 1 : 0;  // (2: off, for A/B runs)
   const dim3 grid((unsigned)(((std::min<long long>(n_groups, (long long)KAMD_NUM_CU * per_cu) + 7) / 8) * 8));  // (a multiple of 8: every group served)
-#define KAMD_RBL(DT)                                                                                                       \
+#define KAMD_RBL_GF(DT, SW)                                                                                                \
   if (g_feat != nullptr)                                                                                                   \
-    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_list_kernel<T, DT, true>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx,  \
-                      weights, img, feat, eps, g_img, g_feat, cov_counts, cov_list, cov_cap, grouped, magic_word, magic, bigwork);  \
+    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_list_kernel<T, DT, true, SW>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx,  \
+                      weights, img, feat, eps, g_img, g_feat, cov_counts, cov_list, cov_cap, grouped, magic_word, magic, bigwork, grad_scale);  \
   else                                                                                                                     \
-    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_list_kernel<T, DT, false>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx, \
-                      weights, img, feat, eps, g_img, g_feat, cov_counts, cov_list, cov_cap, grouped, magic_word, magic, bigwork)
+    KAMD_LAUNCH_TIMED(kamd::K_RASTER_BACKWARD, (raster_backward_list_kernel<T, DT, false, SW>), grid, dim3(256), 0, st, B, H, W, F, D, grad, face_idx, \
+                      weights, img, feat, eps, g_img, g_feat, cov_counts, cov_list, cov_cap, grouped, magic_word, magic, bigwork, grad_scale)
+#define KAMD_RBL(DT)                                                                                                       \
+  if (grad_scale != nullptr) {                                                                                             \
+    KAMD_RBL_GF(DT, true);                                                                                                 \
+  } else {                                                                                                                 \
+    KAMD_RBL_GF(DT, false);                                                                                                \
+  }
   switch (D) {
     case 1: KAMD_RBL(1); break;
     case 2: KAMD_RBL(2); break;
@@ -420,6 +438,7 @@ int rasterize_backward_list_launch(hipStream_t st, int B, int H, int W, int F, i
     default: KAMD_RBL(0); break;
   }
 #undef KAMD_RBL
+#undef KAMD_RBL_GF
   return (int)hipGetLastError();
 }
 
@@ -429,16 +448,17 @@ namespace kamd {
 template <typename T>
 int raster_backward_draw_list(hipStream_t st, int B, int H, int W, int F, int D, const T* grad, const int64_t* face_idx, const T* weights,
                               const T* img, const T* feat, float eps, T* g_img, T* g_feat, const unsigned int* cov_counts,
-                              const unsigned int* cov_list, unsigned int cov_cap, const unsigned int* magic_word, unsigned int* bigwork) {
+                              const unsigned int* cov_list, unsigned int cov_cap, const unsigned int* magic_word, unsigned int* bigwork,
+                              const T* grad_scale) {
   return rasterize_backward_list_launch<T>(st, B, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat, cov_counts, cov_list, cov_cap,
-                                           magic_word, bigwork);
+                                           magic_word, bigwork, grad_scale);
 }
 template int raster_backward_draw_list<float>(hipStream_t, int, int, int, int, int, const float*, const int64_t*, const float*, const float*,
                                               const float*, float, float*, float*, const unsigned int*, const unsigned int*, unsigned int,
-                                              const unsigned int*, unsigned int*);
+                                              const unsigned int*, unsigned int*, const float*);
 template int raster_backward_draw_list<double>(hipStream_t, int, int, int, int, int, const double*, const int64_t*, const double*, const double*,
                                                const double*, float, double*, double*, const unsigned int*, const unsigned int*, unsigned int,
-                                               const unsigned int*, unsigned int*);
+                                               const unsigned int*, unsigned int*, const double*);
 template <typename T>
 int raster2_draw(hipStream_t st, int B, int H, int W, int D, int F_dense, float multiplier, float eps, const T* rec,
                  const tl::Lists& LR, const T* feat, T* interp, int64_t* sel_idx, T* weights, const tl::ClassifyOut& co,
@@ -453,13 +473,16 @@ int raster2_draw(hipStream_t st, int B, int H, int W, int D, int F_dense, float 
 template <typename T>
 int raster_backward_draw(hipStream_t st, int B, int H, int W, int F, int D, const T* grad, const int64_t* face_idx, const T* weights,
                          const T* img, const T* feat, float eps, T* g_img, T* g_feat, const unsigned char* tile_cov,
-                         const unsigned int* row_span) {
-  return rasterize_backward_launch<T>(st, B, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat, tile_cov, row_span);
+                         const unsigned int* row_span, const T* grad_scale) {
+  return rasterize_backward_launch<T>(st, B, H, W, F, D, grad, face_idx, weights, img, feat, eps, g_img, g_feat, tile_cov, row_span,
+                                      grad_scale);
 }
 template int raster_backward_draw<float>(hipStream_t, int, int, int, int, int, const float*, const int64_t*, const float*,
-                                         const float*, const float*, float, float*, float*, const unsigned char*, const unsigned int*);
+                                         const float*, const float*, float, float*, float*, const unsigned char*, const unsigned int*,
+                                         const float*);
 template int raster_backward_draw<double>(hipStream_t, int, int, int, int, int, const double*, const int64_t*, const double*,
-                                          const double*, const double*, float, double*, double*, const unsigned char*, const unsigned int*);
+                                          const double*, const double*, float, double*, double*, const unsigned char*, const unsigned int*,
+                                          const double*);
 template int raster2_draw<float>(hipStream_t, int, int, int, int, int, float, float, const float*, const tl::Lists&, const float*,
                                  float*, int64_t*, float*, const tl::ClassifyOut&, bool);
 template int raster2_draw<double>(hipStream_t, int, int, int, int, int, float, float, const double*, const tl::Lists&,

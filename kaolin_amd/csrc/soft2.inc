@@ -997,11 +997,14 @@ __device__ __forceinline__ int flat_view_of(unsigned int key, unsigned int F, un
 }
 inline unsigned int flat_view_magic(int F) { return F <= 1 ? 0u : (unsigned int)((0x100000000ull + (unsigned long long)F - 1ull) / (unsigned long long)F); }
 
-template <typename T>
+// SW ("scaled weights", weighted_sum's backward fused in): `grad` holds the loss weights W and the incoming gradient of pixel p is
+// *grad_scale * W[p] -- the product weighted_sum2_backward_kernel would have stored, formed at the hits' pixels only.
+template <typename T, bool SW>
 __global__ __launch_bounds__(256) void soft_mask_backward_flat_kernel(
     int H, int W, int F, unsigned int f_magic, const T* __restrict__ grad, const T* __restrict__ soft_mask, HitList2<T> list,
     const T* __restrict__ img, T img_scale, float sigmainv, float multiplier, double inv_multiplier, T* __restrict__ g_img,
-    unsigned int* __restrict__ bigwork /* work + tl::WORK_BIGHASH_WORD of the fused operator's work buffer, or nullptr */) {
+    unsigned int* __restrict__ bigwork /* work + tl::WORK_BIGHASH_WORD of the fused operator's work buffer, or nullptr */,
+    const T* __restrict__ grad_scale /* SW only */) {
   __shared__ int s_runf[4][64];
   __shared__ T s_runv[4][64 * 6];
   // the hot faces' terms go to this XCD's copy of their records (tile_lists.h, WORK_BIGHASH_WORD); uniform, fp32 only
@@ -1021,6 +1024,7 @@ __global__ __launch_bounds__(256) void soft_mask_backward_flat_kernel(
   __syncthreads();
   const unsigned int rounds = s_end[FLAT_SHARDS - 1];
   const double neg_sigma = -1.0 * (double)sigmainv;
+  const T gs = SW ? *grad_scale : (T)1;  // (uniform: a scalar load)
   // Software pipeline over the rounds: a hit's gathers (gradient, mask, the face's vertices) depend on its record, and the
   // arithmetic on the gathers -- two memory round trips per round.  Records are loaded two rounds ahead (stage A), gathers
   // one round ahead (stage B), and the arithmetic of a round runs with both in flight.
@@ -1064,7 +1068,7 @@ __global__ __launch_bounds__(256) void soft_mask_backward_flat_kernel(
       int rem;
       const int b = flat_view_of((unsigned int)v.key, (unsigned int)F, f_magic, &rem);
       const size_t pix = ((size_t)b * H + (a.rec.y >> 16)) * W + (a.rec.y & 0xFFFFu);
-      v.dLdp = grad[pix];
+      v.dLdp = SW ? gs * grad[pix] : grad[pix];
       v.all = soft_mask[pix];
       const size_t s6 = (size_t)v.key * 6;
       const int o = v.e >= 3 ? (v.e - 3) * 2 : v.e * 2;

@@ -76,6 +76,9 @@ class DibrRasterizationCuda(torch.autograd.Function):
         # no zero tensors for the gradients of outputs nobody differentiates (the index output alone is B*H*W*8 bytes)
         ctx.set_materialize_grads(False)
         ctx.cfg = (sigmainv, knum, multiplier, eps)
+        # (metrics.render.weighted_sum differentiates a linear loss of the outputs straight into this node's inputs while the
+        # outputs are as this forward made them)
+        ctx.output_versions = (feats._version, soft_mask._version)
         return feats, soft_mask, face_idx
 
     @staticmethod
