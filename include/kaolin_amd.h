@@ -379,6 +379,44 @@ int kamd_texture_mapping_backward_f64(void* stream, int B, int64_t N, int C, int
                                       double* g_uv);
 
 /* ------------------------------------------------------------------------- */
+/* kaolin.render.lighting: the reduced spherical-gaussian inner product       */
+/* (_C.render.sg.unbatched_reduced_sg_inner_product_{forward,backward}_cuda): */
+/* out (num_sg, 3) = sum over the num_other lobes of the SG inner product.    */
+/* Rows: amplitude (num_sg, 3), direction (num_sg, 3), sharpness (num_sg);    */
+/* amplitude = sharpness = NULL selects the constant lobe (lobe_amplitude,    */
+/* direction, lobe_sharpness) -- cosine_lobe_sg -- and then grad_amplitude /  */
+/* grad_sharpness are not written (pass NULL).  Every output is fully         */
+/* written; num_sg == 0 or num_other == 0 returns without a launch (the       */
+/* caller's outputs are then zeros).  Deterministic: no atomics.  backward's  */
+/* workspace: kamd_sg_reduced_inner_product_backward_workspace(num_sg,        */
+/* num_other, elem_size) bytes (host-only).                                   */
+/* ------------------------------------------------------------------------- */
+size_t kamd_sg_reduced_inner_product_backward_workspace(int64_t num_sg, int num_other, int elem_size);
+int kamd_sg_reduced_inner_product_forward_f32(void* stream, int64_t num_sg, int num_other, const float* amplitude,
+                                              const float* direction, const float* sharpness, double lobe_amplitude,
+                                              double lobe_sharpness, const float* other_amplitude,
+                                              const float* other_direction, const float* other_sharpness, float* out);
+int kamd_sg_reduced_inner_product_forward_f64(void* stream, int64_t num_sg, int num_other, const double* amplitude,
+                                              const double* direction, const double* sharpness, double lobe_amplitude,
+                                              double lobe_sharpness, const double* other_amplitude,
+                                              const double* other_direction, const double* other_sharpness, double* out);
+int kamd_sg_reduced_inner_product_backward_f32(void* stream, int64_t num_sg, int num_other, const float* grad_out,
+                                               const float* amplitude, const float* direction, const float* sharpness,
+                                               double lobe_amplitude, double lobe_sharpness, const float* other_amplitude,
+                                               const float* other_direction, const float* other_sharpness, void* workspace,
+                                               float* grad_amplitude, float* grad_direction, float* grad_sharpness,
+                                               float* grad_other_amplitude, float* grad_other_direction,
+                                               float* grad_other_sharpness);
+int kamd_sg_reduced_inner_product_backward_f64(void* stream, int64_t num_sg, int num_other, const double* grad_out,
+                                               const double* amplitude, const double* direction, const double* sharpness,
+                                               double lobe_amplitude, double lobe_sharpness,
+                                               const double* other_amplitude, const double* other_direction,
+                                               const double* other_sharpness, void* workspace, double* grad_amplitude,
+                                               double* grad_direction, double* grad_sharpness,
+                                               double* grad_other_amplitude, double* grad_other_direction,
+                                               double* grad_other_sharpness);
+
+/* ------------------------------------------------------------------------- */
 /* dibr_rasterization in one call (ours; kaolin/render/mesh/dibr.py:119-209   */
 /* = rasterize with valid faces + dibr_soft_mask over all faces).  Same       */
 /* kernels as the separate entry points, sharing one binning pass: the faces  */

@@ -60,6 +60,7 @@ SIGNATURES = {
     'kamd_profile_read': (_i, [_i, _vp, _vp]),
     'kamd_triangle_distance_work_counters': (_i, [_i, _vp]),
     'kamd_debug_transpose64': (_i, [_vp, _i, _vp, _vp, _i]),
+    'kamd_sg_reduced_inner_product_backward_workspace': (_sz, [_i64, _i, _i]),
 }
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
@@ -110,6 +111,10 @@ for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_triangle_distance_backward_{_t}'] = (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_trianglemeshes_to_voxelgrids_{_t}'] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_trianglemeshes_to_voxelbits_{_t}'] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_sg_reduced_inner_product_forward_{_t}'] = (
+        _i, [_vp, _i64, _i, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_sg_reduced_inner_product_backward_{_t}'] = (
+        _i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp] + [_vp] * 7)
 
 _lock = threading.Lock()
 _lib = None

@@ -1,2 +1,3 @@
 from . import camera  # noqa: F401
 from . import mesh  # noqa: F401
+from . import lighting  # noqa: F401
