@@ -84,7 +84,9 @@ __device__ __forceinline__ double sg_dsinhc_series(double y) {
 
 // the pair's G (without 2 pi) and G'(um) / um; v = s_i d_i + s_j d_j.  The series branch is taken only by wavefronts with a
 // lane at 0 < um < 1 (rare in shading: um >= |s_light - 2.133| for unit normals and lights).  um == 0 is left to the
-// exponential form, which yields inf / NaN there as the reference does.
+// exponential form, which yields inf / NaN there as the reference does.  For that to be the same pairs as in the reference,
+// v is the sum of the two ROUNDED products s_i d_i and s_j d_j (no fma): a lobe that is the exact mirror image of a light
+// then gives v == 0 exactly, where an fma leaves the rounding residue of s_i d_i (um ~ 1e-8 s) and a finite result.
 template <typename T>
 __device__ __forceinline__ void sg_pair(T vx, T vy, T vz, T lm, T& G, T& dG_over_um) {
   const T um2 = fma(vz, vz, fma(vy, vy, vx * vx));
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_reduced_forward_kernel(long lon
     for (int j = 0; j < M; ++j) {   // wave-uniform, in order
       const T sj = osharp[j];
       T G, dG;
-      sg_pair<T>(fma(sj, odir[j * 3 + 0], px), fma(sj, odir[j * 3 + 1], py), fma(sj, odir[j * 3 + 2], pz), s + sj, G, dG);
+      sg_pair<T>(px + sj * odir[j * 3 + 0], py + sj * odir[j * 3 + 1], pz + sj * odir[j * 3 + 2], s + sj, G, dG);
       ax = fma(oamp[j * 3 + 0], G, ax);
       ay = fma(oamp[j * 3 + 1], G, ay);
       az = fma(oamp[j * 3 + 2], G, az);
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_reduced_backward_kernel(
           const int j = j0 + jj;
           const T sj = osharp[j];
           const T ajx = oamp[j * 3 + 0], ajy = oamp[j * 3 + 1], ajz = oamp[j * 3 + 2];
-          const T vx = fma(sj, odir[j * 3 + 0], px), vy = fma(sj, odir[j * 3 + 1], py), vz = fma(sj, odir[j * 3 + 2], pz);
+          const T vx = px + sj * odir[j * 3 + 0], vy = py + sj * odir[j * 3 + 1], vz = pz + sj * odir[j * 3 + 2];
           T G, dG;
           sg_pair<T>(vx, vy, vz, s + sj, G, dG);
           const T h = fma(gaz, ajz, fma(gay, ajy, gax * ajx));

@@ -2,7 +2,12 @@
 of sum(out * grad_out), each with the sum of the absolute values of the terms it adds up (the accumulation slack of
 kaolin_amd.utils.testing.elementwise_mismatch).  Every (row, light) pair is its own term: the parameters are expanded to
 (rows, lights, ...) so that autograd hands back each pair's contribution.  Computed in chunks of rows on the inputs'
-device."""
+device.
+
+``reduced_oracle`` differentiates the textbook exponential form by autograd; its gradients carry a relative error of about
+eps64 / um^2 (1e-8 at um = 1e-4).  ``stable_oracle`` is the analytic, piecewise form without that cancellation, and adds to
+every result ``*_cond``, the sum of |term| (1 + um + lm): an f32 evaluation of exp(um - lm) cannot have a relative error
+below about eps (um + lm), whatever the formula, so that is what a bound at large sharpness scales with."""
 import math
 
 import torch
@@ -59,3 +64,151 @@ def reduced_oracle(a, d, s, oa, od, os_, grad_out=None, pairs_per_chunk=1 << 20,
             res[name] = torch.zeros_like(like)
             res[name + '_abs'] = torch.zeros_like(like)
     return res
+
+
+# ---- analytic, piecewise oracle ------------------------------------------------------------------------------------------
+
+SERIES_BELOW = 1.0     # um below which G'(um) / um is its series
+# (x cosh x - sinh x) / x^3 = sum_k (2k + 2) x^2k / (2k + 3)!: at x = 1 the 14th term is 30 / 31! = 4e-33 of a sum of 0.37
+_DSINHC = [(2 * k + 2) / math.factorial(2 * k + 3) for k in range(14)]
+
+
+def pair_kernel(um, lm):
+    """G = (e^(um - lm) - e^(-um - lm)) / um and D = G'(um) / um (the derivative at fixed lm), float64, elementwise.  No
+    step subtracts nearly equal numbers: G through expm1; D in the exponential form ((E + E2) - G) / um^2 from
+    um = SERIES_BELOW up (at um = 1, (E + E2) - G is 3.09 - 2.35 in units of e^-lm: two bits lost at most) and as 2 e^-lm times the
+    positive-term series below it.  um == 0 gives the limits 2 e^-lm and 2 e^-lm / 3."""
+    E = torch.exp(um - lm)
+    safe = torch.where(um > 0, um, torch.ones_like(um))
+    G = torch.where(um > 0, E * (-torch.expm1(-2.0 * um)) / safe, 2.0 * torch.exp(-lm))
+    big = torch.clamp(um, min=SERIES_BELOW)
+    Gb = torch.exp(big - lm) * (-torch.expm1(-2.0 * big)) / big
+    D_exp = ((torch.exp(big - lm) + torch.exp(-big - lm)) - Gb) / (big * big)
+    y = torch.clamp(um, max=SERIES_BELOW) ** 2
+    p = torch.full_like(y, _DSINHC[-1])
+    for c in reversed(_DSINHC[:-1]):
+        p = p * y + c
+    D = torch.where(um >= SERIES_BELOW, D_exp, 2.0 * torch.exp(-lm) * p)
+    return G, D
+
+
+def stable_oracle(a, d, s, oa, od, os_, grad_out=None, pairs_per_chunk=1 << 20, rows=None):
+    """The analytic oracle: dict of out, out_abs, out_cond and (with grad_out) ga, gd, gs, goa, god, gos, each with _abs
+    (sum of |term|) and _cond (sum of |term| (1 + um + lm)).  One term per (row, light) pair and component:
+        out 2 pi a_i a_j G      ga 2 pi g a_j G      gd 2 pi s_i q v      goa 2 pi g a_i G      god 2 pi s_j q v
+    with h = sum_c g a_i a_j and q = h G'(um) / um; the sharpness gradients' term is the difference of two pieces,
+    2 pi q (v . d) and 2 pi h G, which are accumulated apart (by the kernels and by autograd alike) and nearly cancel for
+    aligned sharp lobes: their _abs and _cond use |piece 1| + |piece 2|.  Inputs are promoted to float64; `rows` as in
+    reduced_oracle."""
+    a, d, s, oa, od, os_ = (t.detach().double() for t in (a, d, s, oa, od, os_))
+    n, m = a.shape[0], oa.shape[0]
+    tp = 2.0 * math.pi
+    with_grad = grad_out is not None
+    row_names = ('out', 'ga', 'gd', 'gs') if with_grad else ('out',)
+    col_like = {'goa': oa, 'god': od, 'gos': os_}
+    res = {}
+    if with_grad:
+        for k, like in col_like.items():
+            for sfx in ('', '_abs', '_cond'):
+                res[k + sfx] = torch.zeros_like(like)
+    parts = {k + sfx: [] for k in row_names for sfx in ('', '_abs', '_cond')}
+    chunk = max(1, pairs_per_chunk // max(m, 1))
+    for r0 in range(0, n, chunk):
+        r1 = min(n, r0 + chunk)
+        ai, di, si = a[r0:r1, None, :], d[r0:r1, None, :], s[r0:r1, None]
+        v = si[..., None] * di + os_[None, :, None] * od[None]
+        um = torch.sqrt((v * v).sum(-1))
+        lm = si + os_[None]
+        G, D = pair_kernel(um, lm)
+        w = (1.0 + um + lm)
+        keep = None if rows is None else rows[(rows >= r0) & (rows < r1)] - r0
+
+        def row_add(name, t, t_abs=None):
+            t_abs = t.abs() if t_abs is None else t_abs
+            wt = w if t.dim() == 2 else w[..., None]
+            for sfx, x in (('', t), ('_abs', t_abs), ('_cond', t_abs * wt)):
+                x = x.sum(1)
+                parts[name + sfx].append(x if keep is None else x[keep])
+
+        def col_add(name, t, t_abs=None):
+            t_abs = t.abs() if t_abs is None else t_abs
+            wt = w if t.dim() == 2 else w[..., None]
+            res[name] += t.sum(0)
+            res[name + '_abs'] += t_abs.sum(0)
+            res[name + '_cond'] += (t_abs * wt).sum(0)
+
+        row_add('out', tp * ai * oa[None] * G[..., None])
+        if not with_grad:
+            continue
+        g = grad_out[r0:r1].detach().double()[:, None, :]
+        gai = g * ai
+        h = (gai * oa[None]).sum(-1)
+        q = h * D
+        hG = tp * h * G
+        row_add('ga', tp * g * oa[None] * G[..., None])
+        row_add('gd', tp * (si * q)[..., None] * v)
+        p1 = tp * q * (v * di).sum(-1)
+        row_add('gs', p1 - hG, p1.abs() + hG.abs())
+        col_add('goa', tp * gai * G[..., None])
+        col_add('god', tp * (os_[None] * q)[..., None] * v)
+        p1 = tp * q * (v * od[None]).sum(-1)
+        col_add('gos', p1 - hG, p1.abs() + hG.abs())
+    like = {'out': a, 'ga': a, 'gd': d, 'gs': s}
+    for name in row_names:
+        for sfx in ('', '_abs', '_cond'):
+            if parts[name + sfx]:
+                res[name + sfx] = torch.cat(parts[name + sfx])
+            else:
+                shape = list(like[name].shape)
+                shape[0] = 0 if rows is None else len(rows)
+                res[name + sfx] = torch.zeros(shape, dtype=torch.float64, device=a.device)
+    return res
+
+
+# ---- the conditioned bound -----------------------------------------------------------------------------------------------
+
+TOL = {torch.float32: 1e-5, torch.float64: 1e-10}
+
+
+def conditioned_mismatch(a, b, abs_sum, cond, k_cond, tol=None, sum_ulps=64.0, allow_nan=None):
+    """`a` (the result under test) against the oracle's `b`:
+        |a - b| <= tol |b| + tol median|b != 0| + sum_ulps eps sum|terms| + k_cond eps cond,      eps of a's dtype
+    the first three terms being kaolin_amd.utils.testing.elementwise_mismatch's bound.  `allow_nan` (bool mask, optional):
+    the elements where `a` must be NaN; they are left out of the comparison and of the median, and NaN anywhere else fails.
+    -> (message or None, number of elements that pass only thanks to the cond term, max |a - b| / (eps cond))."""
+    eps = float(torch.finfo(a.dtype).eps)
+    tol = TOL[a.dtype] if tol is None else tol
+    a, b, abs_sum, cond = (t.detach().double().cpu() for t in (a, b, abs_sum, cond))
+    if a.shape != b.shape:
+        return f'shape {tuple(a.shape)} vs {tuple(b.shape)}', 0, float('nan')
+    live = torch.ones_like(a, dtype=torch.bool) if allow_nan is None else ~allow_nan.cpu()
+    if allow_nan is not None and not bool(torch.isnan(a[~live]).all()):
+        return f'{int((~torch.isnan(a[~live])).sum())} of {int((~live).sum())} elements that must be NaN are not', 0, float('nan')
+    nz = b[live & (b != 0)].abs()
+    floor = float(nz.median()) if nz.numel() else 0.0
+    plain = tol * b.abs() + tol * floor + sum_ulps * eps * abs_sum
+    bound = plain + k_cond * eps * cond
+    err = (a - b).abs()
+    bad = live & ~(err <= bound)                                       # NaN outside allow_nan fails
+    needed = int((live & (err > plain) & (err <= bound)).sum())
+    units = torch.where(cond > 0, err / (eps * cond.clamp(min=1e-300)), torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+    units = float(units[live].max()) if bool(live.any()) else 0.0
+    if not bool(bad.any()):
+        return None, needed, units
+    excess = torch.where(bad, torch.nan_to_num(err, nan=float('inf')) / bound.clamp(min=1e-300), torch.zeros_like(a))
+    i = int(excess.reshape(-1).argmax())
+    idx = tuple(int(t) for t in torch.unravel_index(torch.tensor(i), a.shape)) if a.dim() else ()
+    return (f'{int(bad.sum())} of {a.numel()} elements outside tol|b| + tol*{floor:.3e} + {sum_ulps:g} eps sum|terms| + '
+            f'{k_cond:.3g} eps cond; worst at {idx}: {float(a.reshape(-1)[i])!r} vs {float(b.reshape(-1)[i])!r} '
+            f'({float(excess.reshape(-1)[i]):.2f}x the bound; sum|terms| {float(abs_sum.reshape(-1)[i]):.4e}, cond '
+            f'{float(cond.reshape(-1)[i]):.4e}, {float(err.reshape(-1)[i]) / max(eps * float(cond.reshape(-1)[i]), 1e-300):.3g} '
+            f'eps cond)'), needed, units
+
+
+def error_units(a, b, cond):
+    """max |a - b| / (eps(a.dtype) cond) over the elements (0 where both vanish): how K_ref of the fixture is measured."""
+    eps = float(torch.finfo(a.dtype).eps)
+    err = (a.detach().double().cpu() - b.detach().double().cpu()).abs()
+    cond = cond.detach().double().cpu()
+    u = torch.where(cond > 0, err / (eps * cond.clamp(min=1e-300)), torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+    return float(u.max()) if u.numel() else 0.0
