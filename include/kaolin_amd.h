@@ -709,6 +709,40 @@ int kamd_trianglemeshes_to_voxelbits_f64(void* stream, int B, int V, int F, int 
                                          uint32_t* bits);
 
 /* ------------------------------------------------------------------------- */
+/* ops.voxelgrid.fill(voxelgrids) -> bool (N,X,Y,Z): the walls (value != 0:    */
+/* NaN is a wall, -0.0 is empty) and every empty voxel with no path of         */
+/* face-adjacent empty voxels to an empty voxel of the six boundary faces.     */
+/* The reference runs SciPy's binary_fill_holes on the host and raises on a    */
+/* GPU tensor (kaolin/ops/voxelgrid.py:143-206); this is an exact flood fill   */
+/* over two bit grids (csrc/voxelgrid_fill.hip).  voxelgrids: element strides  */
+/* stride_n/x/y/z (any layout); filled: N*X*Y*Z contiguous bytes of 0/1, fully */
+/* written; workspace: kamd_voxelgrid_fill_workspace(N,X,Y,Z) bytes, 4-byte    */
+/* aligned.  The call launches passes until one changes nothing and reads a    */
+/* word back every few passes: it SYNCHRONISES the stream (not capturable in a */
+/* graph).  host_stats (host int32[3], may be NULL): passes that worked,       */
+/* passes launched, host reads.  f16: voxelgrids points to IEEE half values.   */
+/* ------------------------------------------------------------------------- */
+size_t kamd_voxelgrid_fill_workspace(int64_t N, int X, int Y, int Z);
+int kamd_voxelgrid_fill_u8(void* stream, int64_t N, int X, int Y, int Z, const uint8_t* voxelgrids, int64_t stride_n,
+                           int64_t stride_x, int64_t stride_y, int64_t stride_z, uint8_t* filled, void* workspace,
+                           int32_t* host_stats);
+int kamd_voxelgrid_fill_i32(void* stream, int64_t N, int X, int Y, int Z, const int32_t* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, uint8_t* filled, void* workspace,
+                            int32_t* host_stats);
+int kamd_voxelgrid_fill_i64(void* stream, int64_t N, int X, int Y, int Z, const int64_t* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, uint8_t* filled, void* workspace,
+                            int32_t* host_stats);
+int kamd_voxelgrid_fill_f16(void* stream, int64_t N, int X, int Y, int Z, const void* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, uint8_t* filled, void* workspace,
+                            int32_t* host_stats);
+int kamd_voxelgrid_fill_f32(void* stream, int64_t N, int X, int Y, int Z, const float* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, uint8_t* filled, void* workspace,
+                            int32_t* host_stats);
+int kamd_voxelgrid_fill_f64(void* stream, int64_t N, int X, int Y, int Z, const double* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, uint8_t* filled, void* workspace,
+                            int32_t* host_stats);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -1,5 +1,7 @@
 """Host shims of ``kaolin._C.ops`` operators, plus the fused voxelizer (the reference has no ``kaolin._C`` operator for
 it: the op is pure PyTorch, kaolin/ops/conversions/trianglemesh.py:29-110; that entry point exists only on our side)."""
+import ctypes
+
 import torch
 
 from .. import _lib
@@ -150,6 +152,40 @@ def mesh_to_spc_cuda(face_vertices, level):
         _lib.check(lib.kamd_mesh_to_spc_results(sp, n, level, _lib.ptr(face_vertices), _lib.ptr(ws), num_voxels, octree_bytes,
                                                 _lib.ptr(octree), _lib.ptr(face_ids), _lib.ptr(bary)), fn)
     return [octree, face_ids, bary]
+
+
+_FILL_SUFFIX = {torch.bool: 'u8', torch.uint8: 'u8', torch.int32: 'i32', torch.int64: 'i64', torch.float16: 'f16',
+                torch.float32: 'f32', torch.float64: 'f64'}
+
+
+def voxelgrid_fill_cuda(voxelgrids, stats=None):
+    """voxelgrids (N, X, Y, Z), any strides; bool / uint8 / int32 / int64 / half / float / double -> bool (N, X, Y, Z): the
+    walls (value != 0) and every cavity the outside does not reach through faces (csrc/voxelgrid_fill.hip).  No reference
+    operator: kaolin.ops.voxelgrid.fill raises on a GPU tensor.  The call synchronises the current stream (the host reads
+    a flag every few passes), so it cannot be captured in a graph.  ``stats``: a dict that receives ``passes`` (passes that
+    worked), ``launched`` and ``polls``."""
+    fn = 'voxelgrid_fill_cuda'
+    torch_check(voxelgrids.is_cuda, f'{fn}: voxelgrids must be a CUDA tensor')
+    torch_check(voxelgrids.dim() == 4, f'{fn}: voxelgrids must of size {{batch_size, X, Y, Z}}')
+    sfx = _FILL_SUFFIX.get(voxelgrids.dtype)
+    if sfx is None:
+        raise RuntimeError(f'"{fn}" not implemented for \'{_lib.pretty_dtype(voxelgrids.dtype)}\'')
+    N, X, Y, Z = voxelgrids.shape
+    torch_check(max(X, Y, Z) < 2 ** 31, f'{fn}: a grid dimension exceeds the 32-bit range')
+    dev = voxelgrids.device
+    lib = _lib.load()
+    host = (ctypes.c_int32 * 3)()
+    with _lib.on_device(dev):
+        out = torch.empty((N, X, Y, Z), dtype=torch.bool, device=dev)
+        if out.numel() > 0:
+            ws = _lib.workspace(lib.kamd_voxelgrid_fill_workspace(N, X, Y, Z), dev)
+            st = getattr(lib, f'kamd_voxelgrid_fill_{sfx}')(
+                _lib.stream_ptr(dev), N, X, Y, Z, _lib.ptr(voxelgrids), *voxelgrids.stride(), _lib.ptr(out), _lib.ptr(ws),
+                ctypes.cast(host, ctypes.c_void_p))
+            _lib.check(st, fn)
+    if stats is not None:
+        stats.update(passes=host[0], launched=host[1], polls=host[2])
+    return out
 
 
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)

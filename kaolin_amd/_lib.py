@@ -61,10 +61,13 @@ SIGNATURES = {
     'kamd_triangle_distance_work_counters': (_i, [_i, _vp]),
     'kamd_debug_transpose64': (_i, [_vp, _i, _vp, _vp, _i]),
     'kamd_sg_reduced_inner_product_backward_workspace': (_sz, [_i64, _i, _i]),
+    'kamd_voxelgrid_fill_workspace': (_sz, [_i64, _i, _i, _i]),
 }
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_sided_distance_backward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp])
+for _t in ('u8', 'i32', 'i64', 'f16', 'f32', 'f64'):
+    SIGNATURES[f'kamd_voxelgrid_fill_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_packed_rasterize_forward_{_t}'] = (
         _i, [_vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp])
