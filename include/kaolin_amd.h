@@ -743,6 +743,45 @@ int kamd_voxelgrid_fill_f64(void* stream, int64_t N, int X, int Y, int Z, const 
                             int32_t* host_stats);
 
 /* ------------------------------------------------------------------------- */
+/* ops.conversions.marching_tetrahedra, one item of the batch (reference: ~25  */
+/* torch kernels, kaolin/ops/conversions/tetmesh.py; csrc/marching_tetrahedra  */
+/* .hip has the pipeline).  tets: (T,4) int64 contiguous, 16-byte aligned;     */
+/* vertices (V,3), sdf (V) contiguous; V < 2^32.  A vertex is occupied when    */
+/* sdf > 0; a tet with a corner outside [0,V) is ignored (the shim raises      */
+/* before it gets here).  Result sizes depend on the data, so the sequence is  */
+/*   1. classify: workspace <- occupancy bits, the case of every tet, scanned  */
+/*      counts; host_counts[0..1] <- tets that emit one / two triangles.       */
+/*   2. edges (skip when both are 0): edges_workspace <- the valid tets in tet */
+/*      order, the sorted unique crossing edges; *host_num_unique <- their     */
+/*      number = the number of output vertices.                                */
+/*   3. emit: verts (num_unique,3), edges (num_unique,2) int64 = the (a,b),    */
+/*      a < b, each vertex interpolates, faces (n_one + 2 n_two, 3) int64,     */
+/*      tet_idx (n_one + 2 n_two) int64 or NULL.                               */
+/* Steps 1 and 2 each read a count back: they SYNCHRONISE the stream (not      */
+/* capturable in a graph).  The *_workspace queries are host arithmetic; 0 =   */
+/* nothing to do.  backward: grad_vertices (V,3) and grad_sdf (V) must be      */
+/* zeroed by the caller; accumulated with fp atomic adds.                      */
+/* ------------------------------------------------------------------------- */
+size_t kamd_marching_tetrahedra_workspace(int64_t T, int64_t V);
+size_t kamd_marching_tetrahedra_edges_workspace(int64_t n_one, int64_t n_two);
+int kamd_marching_tetrahedra_classify_f32(void* stream, int64_t T, int64_t V, const int64_t* tets, const float* sdf,
+                                          void* workspace, int64_t* host_counts);
+int kamd_marching_tetrahedra_classify_f64(void* stream, int64_t T, int64_t V, const int64_t* tets, const double* sdf,
+                                          void* workspace, int64_t* host_counts);
+int kamd_marching_tetrahedra_edges(void* stream, int64_t T, int64_t V, const int64_t* tets, const void* workspace, int64_t n_one,
+                                   int64_t n_two, void* edges_workspace, int64_t* host_num_unique);
+int kamd_marching_tetrahedra_emit_f32(void* stream, int64_t V, const int64_t* tets, const float* vertices, const float* sdf,
+                                      const void* edges_workspace, int64_t n_one, int64_t n_two, int64_t num_unique,
+                                      float* verts, int64_t* edges, int64_t* faces, int64_t* tet_idx);
+int kamd_marching_tetrahedra_emit_f64(void* stream, int64_t V, const int64_t* tets, const double* vertices, const double* sdf,
+                                      const void* edges_workspace, int64_t n_one, int64_t n_two, int64_t num_unique,
+                                      double* verts, int64_t* edges, int64_t* faces, int64_t* tet_idx);
+int kamd_marching_tetrahedra_backward_f32(void* stream, int64_t num_edges, int64_t V, const int64_t* edges, const float* vertices,
+                                          const float* sdf, const float* grad_verts, float* grad_vertices, float* grad_sdf);
+int kamd_marching_tetrahedra_backward_f64(void* stream, int64_t num_edges, int64_t V, const int64_t* edges, const double* vertices,
+                                          const double* sdf, const double* grad_verts, double* grad_vertices, double* grad_sdf);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -188,7 +188,103 @@ def voxelgrid_fill_cuda(voxelgrids, stats=None):
     return out
 
 
+def check_tets_in_range(tets, num_vertices, fn='marching_tetrahedra'):
+    """tets (T, 4) of an integer dtype on any device: raises IndexError when an entry lies outside [0, num_vertices).  Pure
+    torch (one min / max pass and one host read); called before any kernel sees the ids -- an id out of range would make the
+    HIP path read outside its buffers."""
+    torch_check(tets.dim() == 2 and tets.size(1) == 4, f'{fn}: tets must of size {{num_tetrahedrons, 4}}')
+    torch_check(not tets.dtype.is_floating_point and not tets.dtype.is_complex, f'{fn}: tets must be of an integer type')
+    if tets.numel() == 0:
+        return
+    lo, hi = torch.stack(torch.aminmax(tets)).tolist()
+    if lo < 0 or hi >= num_vertices:
+        raise IndexError(f'{fn}: tets hold the index {lo if lo < 0 else hi}, outside [0, num_vertices = {num_vertices})')
+
+
+def _marching_tetrahedra_args(fn, tensors):
+    dev = tensors[0][1].device
+    for name, t in tensors:
+        torch_check(t.is_cuda, f'{fn}: {name} must be a CUDA tensor')
+        torch_check(t.device == dev, f'{fn}: {name} must be on the same device as {tensors[0][0]}')
+    return dev
+
+
+def marching_tetrahedra_cuda(vertices, tets, sdf, return_tet_idx=False):
+    """One item of kaolin.ops.conversions.marching_tetrahedra on the HIP pipeline of csrc/marching_tetrahedra.hip (the reference
+    has no ``_C`` operator here: its tetmesh.py is a chain of torch kernels).  vertices (V, 3) and sdf (V) float32 or float64,
+    tets (T, 4) int64 -> verts (Nv, 3), faces (F, 3) int64, edges (Nv, 2) int64 [, tet_idx (F) int64]: vertex i lies on the edge
+    ``edges[i] = (a, b)``, a < b -- what marching_tetrahedra_backward_cuda needs.  Result sizes depend on the data: the host
+    reads the number of surface tets and then the number of vertices, so the call synchronises the current stream twice and
+    cannot be captured in a graph (like the reference, whose torch.unique and mask indexing synchronise)."""
+    fn = 'marching_tetrahedra_cuda'
+    dev = _marching_tetrahedra_args(fn, (('vertices', vertices), ('tets', tets), ('sdf', sdf)))
+    torch_check(vertices.dim() == 2 and vertices.size(1) == 3, f'{fn}: vertices must of size {{num_vertices, 3}}')
+    torch_check(sdf.dim() == 1 and sdf.size(0) == vertices.size(0), f'{fn}: sdf must of size {{num_vertices}}')
+    torch_check(tets.dtype == torch.long, f'{fn}: tets must be long')
+    torch_check(sdf.dtype == vertices.dtype, f'{fn}: expected vertices and sdf to have the same scalar type')
+    sfx = _lib.dtype_suffix(vertices.dtype, fn)
+    V, T = vertices.size(0), tets.size(0) if tets.dim() == 2 else 0
+    torch_check(V < 2 ** 32, f'{fn}: more than 2^32 - 1 vertices')
+    check_tets_in_range(tets, V, fn)
+    v, s, t = vertices.detach().contiguous(), sdf.detach().contiguous(), tets.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()                                          # the kernels read a tet as two 16-byte words
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    n_one = n_two = nu = 0
+    with _lib.on_device(dev):
+        if T > 0 and V > 0:
+            ws = _lib.workspace(lib.kamd_marching_tetrahedra_workspace(T, V), dev)
+            counts = (ctypes.c_int64 * 2)()
+            _lib.check(getattr(lib, f'kamd_marching_tetrahedra_classify_{sfx}')(
+                sp, T, V, _lib.ptr(t), _lib.ptr(s), _lib.ptr(ws), ctypes.cast(counts, ctypes.c_void_p)), fn)
+            n_one, n_two = counts[0], counts[1]                # data-dependent sizes: the first host read
+        if n_one + n_two > 0:
+            ews = _lib.workspace(lib.kamd_marching_tetrahedra_edges_workspace(n_one, n_two), dev)
+            unique = ctypes.c_int64(0)
+            _lib.check(lib.kamd_marching_tetrahedra_edges(sp, T, V, _lib.ptr(t), _lib.ptr(ws), n_one, n_two, _lib.ptr(ews),
+                                                          ctypes.cast(ctypes.pointer(unique), ctypes.c_void_p)), fn)
+            nu = unique.value                                  # ... and the second
+        nf = n_one + 2 * n_two
+        verts = torch.empty((nu, 3), dtype=v.dtype, device=dev)
+        edges = torch.empty((nu, 2), dtype=torch.long, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.long, device=dev)
+        tet_idx = torch.empty(nf, dtype=torch.long, device=dev) if return_tet_idx else None
+        if nf > 0:
+            _lib.check(getattr(lib, f'kamd_marching_tetrahedra_emit_{sfx}')(
+                sp, V, _lib.ptr(t), _lib.ptr(v), _lib.ptr(s), _lib.ptr(ews), n_one, n_two, nu, _lib.ptr(verts), _lib.ptr(edges),
+                _lib.ptr(faces), _lib.ptr(tet_idx)), fn)
+    return (verts, faces, edges, tet_idx) if return_tet_idx else (verts, faces, edges)
+
+
+def marching_tetrahedra_backward_cuda(grad_verts, vertices, sdf, edges):
+    """grad_verts (Nv, 3), vertices (V, 3), sdf (V), edges (Nv, 2) of marching_tetrahedra_cuda -> grad_vertices (V, 3), grad_sdf (V):
+    one thread per output vertex, atomic adds into the two zeroed results."""
+    fn = 'marching_tetrahedra_backward_cuda'
+    dev = _marching_tetrahedra_args(fn, (('grad_verts', grad_verts), ('vertices', vertices), ('sdf', sdf), ('edges', edges)))
+    nu, V = edges.size(0), vertices.size(0)
+    torch_check(vertices.dim() == 2 and vertices.size(1) == 3, f'{fn}: vertices must of size {{num_vertices, 3}}')
+    torch_check(tuple(sdf.shape) == (V,), f'{fn}: sdf must of size {{num_vertices}}')
+    torch_check(tuple(edges.shape) == (nu, 2) and edges.dtype == torch.long, f'{fn}: edges must be long, of size {{num_edges, 2}}')
+    torch_check(tuple(grad_verts.shape) == (nu, 3), f'{fn}: grad_verts must of size {{num_edges, 3}}')
+    torch_check(sdf.dtype == vertices.dtype and grad_verts.dtype == vertices.dtype,
+                f'{fn}: expected grad_verts, vertices and sdf to have the same scalar type')
+    sfx = _lib.dtype_suffix(vertices.dtype, fn)
+    torch_check(V < 2 ** 32, f'{fn}: more than 2^32 - 1 vertices')
+    g, v, s, e = grad_verts.contiguous(), vertices.detach().contiguous(), sdf.detach().contiguous(), edges.contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_vertices = torch.zeros((V, 3), dtype=v.dtype, device=dev)
+        grad_sdf = torch.zeros(V, dtype=v.dtype, device=dev)
+        if nu > 0 and V > 0:
+            _lib.check(getattr(lib, f'kamd_marching_tetrahedra_backward_{sfx}')(
+                _lib.stream_ptr(dev), nu, V, _lib.ptr(e), _lib.ptr(v), _lib.ptr(s), _lib.ptr(g), _lib.ptr(grad_vertices),
+                _lib.ptr(grad_sdf)), fn)
+    return grad_vertices, grad_sdf
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda)
-conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda)
+conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
+                                     marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda)

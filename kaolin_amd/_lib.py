@@ -62,6 +62,9 @@ SIGNATURES = {
     'kamd_debug_transpose64': (_i, [_vp, _i, _vp, _vp, _i]),
     'kamd_sg_reduced_inner_product_backward_workspace': (_sz, [_i64, _i, _i]),
     'kamd_voxelgrid_fill_workspace': (_sz, [_i64, _i, _i, _i]),
+    'kamd_marching_tetrahedra_workspace': (_sz, [_i64, _i64]),
+    'kamd_marching_tetrahedra_edges_workspace': (_sz, [_i64, _i64]),
+    'kamd_marching_tetrahedra_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
 }
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
@@ -69,6 +72,9 @@ for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
 for _t in ('u8', 'i32', 'i64', 'f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_voxelgrid_fill_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_marching_tetrahedra_classify_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_marching_tetrahedra_emit_{_t}'] = (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_marching_tetrahedra_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_packed_rasterize_forward_{_t}'] = (
         _i, [_vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_rasterize_backward_{_t}'] = (

@@ -1,2 +1,4 @@
 from .trianglemesh import trianglemeshes_to_voxelgrids, unbatched_mesh_to_spc  # noqa: F401
 from . import trianglemesh  # noqa: F401
+from .tetmesh import marching_tetrahedra  # noqa: F401
+from . import tetmesh  # noqa: F401

@@ -259,3 +259,21 @@ def sphere_scene(level=16, num_views=1, device='cpu', dtype=torch.float, seed=0,
     uv = torch.rand((1, f.shape[0], 3, 2), generator=g, dtype=torch.float).to(dtype).repeat(num_views, 1, 1, 1)
     ones = torch.ones((num_views, f.shape[0], 3, 1), dtype=dtype)
     return fz.to(device), fimg.to(device), [uv.to(device), ones.to(device)], nz.to(device)
+
+
+def kuhn_grid(n, dtype=torch.float):
+    """The Kuhn (Freudenthal) tetrahedral grid of the unit cube: n^3 cells of 6 tets each, all sharing the cell's main
+    diagonal (one tet per order in which the three axes are walked from the cell's low corner to its high corner).
+    Returns (vertices ((n + 1)^3, 3) in [0, 1]^3, tets (6 n^3, 4) int64); vertex (i, j, k) has id (i (n + 1) + j) (n + 1) + k."""
+    m = n + 1
+    r = torch.arange(m, dtype=torch.float64) / n
+    vertices = torch.stack(torch.meshgrid(r, r, r, indexing='ij'), dim=-1).reshape(-1, 3).to(dtype)
+    c = torch.arange(n, dtype=torch.long)
+    base = ((c.view(-1, 1, 1) * m + c.view(1, -1, 1)) * m + c.view(1, 1, -1)).reshape(-1)
+    step = (m * m, m, 1)
+    tets = []
+    for order in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+        v1 = base + step[order[0]]
+        v2 = v1 + step[order[1]]
+        tets.append(torch.stack([base, v1, v2, v2 + step[order[2]]], dim=-1))
+    return vertices, torch.stack(tets, dim=1).reshape(-1, 4)
