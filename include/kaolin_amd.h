@@ -782,6 +782,49 @@ int kamd_marching_tetrahedra_backward_f64(void* stream, int64_t num_edges, int64
                                           const double* sdf, const double* grad_verts, double* grad_vertices, double* grad_sdf);
 
 /* ------------------------------------------------------------------------- */
+/* ops.mesh.subdivide_tetmesh (reference: torch.unique(dim=0) over the 6 T     */
+/* edge rows and a chain of gathers / cats / stacks, kaolin/ops/mesh/tetmesh   */
+/* .py; csrc/subdivide_tetmesh.hip has the pipeline).  tets: (T,4) int64       */
+/* contiguous, 16-byte aligned, every id in [0,V) (the shim raises before it   */
+/* gets here), V < 2^32.  Topology, once per call:                             */
+/*   1. edges: workspace <- the 6 T keys min << 32 | max, sorted, and the      */
+/*      unique ones; *host_num_edges <- E.  Reads E back: SYNCHRONISES the     */
+/*      stream (not capturable in a graph).                                    */
+/*   2. emit: edges (E,2) int64 = the (min,max) pairs in ascending order,      */
+/*      new_tets (8 T,4) int64: eight blocks of T rows in tet order, edge e    */
+/*      being vertex V + e.  Both 16-byte aligned, fully written.              */
+/* The workspace query is host arithmetic; 0 = nothing to do (T = 0).          */
+/* Midpoints, the whole batch per call; vertices (B,V,3) and features (B,V,D)  */
+/* with contiguous items `*_batch_stride` elements apart (0: an expanded       */
+/* batch), features may be NULL (D ignored):                                   */
+/* `edges` (E,2): every id in [0,V), gathered by UNCHECKED (the shim checks    */
+/* edges that do not come from step 2):                                       */
+/*   forward: new_vertices (B,V+E,3), new_features (B,V+E,D) contiguous, rows  */
+/*      [0,V) copied, row V + e = (x[min] + x[max]) * 0.5; one launch.         */
+/*   backward: grad_new_* (B,V+E,.) contiguous, either may be NULL (its        */
+/*      result is then not touched); grad_* (B,V,.) fully written: g[v] + the  */
+/*      halves of the edges with min = v (a plain store), then fp atomic adds  */
+/*      of the halves into the max ends.                                       */
+/* ------------------------------------------------------------------------- */
+size_t kamd_subdivide_tetmesh_workspace(int64_t T, int64_t V);
+int kamd_subdivide_tetmesh_edges(void* stream, int64_t T, int64_t V, const int64_t* tets, void* workspace,
+                                 int64_t* host_num_edges);
+int kamd_subdivide_tetmesh_emit(void* stream, int64_t T, int64_t V, const int64_t* tets, const void* workspace, int64_t num_edges,
+                                int64_t* edges, int64_t* new_tets);
+int kamd_tetmesh_midpoints_forward_f32(void* stream, int64_t B, int64_t V, int64_t E, int64_t D, const float* vertices,
+                                       int64_t vertices_batch_stride, const float* features, int64_t features_batch_stride,
+                                       const int64_t* edges, float* new_vertices, float* new_features);
+int kamd_tetmesh_midpoints_forward_f64(void* stream, int64_t B, int64_t V, int64_t E, int64_t D, const double* vertices,
+                                       int64_t vertices_batch_stride, const double* features, int64_t features_batch_stride,
+                                       const int64_t* edges, double* new_vertices, double* new_features);
+int kamd_tetmesh_midpoints_backward_f32(void* stream, int64_t B, int64_t V, int64_t E, int64_t D, const float* grad_new_vertices,
+                                        const float* grad_new_features, const int64_t* edges, float* grad_vertices,
+                                        float* grad_features);
+int kamd_tetmesh_midpoints_backward_f64(void* stream, int64_t B, int64_t V, int64_t E, int64_t D, const double* grad_new_vertices,
+                                        const double* grad_new_features, const int64_t* edges, double* grad_vertices,
+                                        double* grad_features);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

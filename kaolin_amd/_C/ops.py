@@ -283,8 +283,127 @@ def marching_tetrahedra_backward_cuda(grad_verts, vertices, sdf, edges):
     return grad_vertices, grad_sdf
 
 
+def subdivide_tetmesh_cuda(tets, num_vertices):
+    """The topology of kaolin.ops.mesh.subdivide_tetmesh on the HIP pipeline of csrc/subdivide_tetmesh.hip (the reference has no
+    ``_C`` operator here: its tetmesh.py is torch.unique(dim=0) and a chain of gathers).  tets (T, 4) int64, ids in
+    [0, num_vertices) -> edges (E, 2) int64: the unique (min, max) edges in ascending order, edge e being the new vertex
+    ``num_vertices + e``; new_tets (8 T, 4) int64.  The host reads E back: the call synchronises the current stream once and cannot
+    be captured in a graph (like the reference, whose torch.unique synchronises)."""
+    fn = 'subdivide_tetmesh_cuda'
+    V = int(num_vertices)
+    check_tets_in_range(tets, V, fn)
+    torch_check(tets.is_cuda, f'{fn}: tets must be a CUDA tensor')
+    torch_check(tets.dtype == torch.long, f'{fn}: tets must be long')
+    torch_check(0 <= V < 2 ** 32, f'{fn}: more than 2^32 - 1 vertices')
+    dev, T = tets.device, tets.size(0)
+    t = tets.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()                                          # the kernels read a tet as two 16-byte words
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        num_edges = 0
+        if T > 0:
+            ws = _lib.workspace(lib.kamd_subdivide_tetmesh_workspace(T, V), dev)
+            count = ctypes.c_int64(0)
+            _lib.check(lib.kamd_subdivide_tetmesh_edges(sp, T, V, _lib.ptr(t), _lib.ptr(ws),
+                                                        ctypes.cast(ctypes.pointer(count), ctypes.c_void_p)), fn)
+            num_edges = count.value                            # data-dependent size: the one host read
+        edges = torch.empty((num_edges, 2), dtype=torch.long, device=dev)
+        new_tets = torch.empty((8 * T, 4), dtype=torch.long, device=dev)
+        if T > 0:
+            _lib.check(lib.kamd_subdivide_tetmesh_emit(sp, T, V, _lib.ptr(t), _lib.ptr(ws), num_edges, _lib.ptr(edges),
+                                                       _lib.ptr(new_tets)), fn)
+    return edges, new_tets
+
+
+def _tetmesh_midpoints_args(fn, named, edges, num_vertices, check_edges):
+    """named: ((name, tensor or None, channels or None), ...) of (B, rows, channels) tensors of one dtype on edges' device.
+    check_edges: raise IndexError when an entry of edges lies outside [0, num_vertices) -- the kernels gather by them unchecked
+    (one torch min / max pass and a host read; the autograd function skips it for the edges the topology stage has just made)."""
+    torch_check(edges.is_cuda, f'{fn}: edges must be a CUDA tensor')
+    torch_check(edges.dim() == 2 and edges.size(1) == 2 and edges.dtype == torch.long, f'{fn}: edges must be long, of size {{num_edges, 2}}')
+    torch_check(edges.is_contiguous(), f'{fn}: edges must be contiguous')
+    if check_edges and edges.numel() > 0:
+        lo, hi = torch.stack(torch.aminmax(edges)).tolist()
+        if lo < 0 or hi >= num_vertices:
+            raise IndexError(f'{fn}: edges hold the index {lo if lo < 0 else hi}, outside [0, num_vertices = {num_vertices})')
+    first = next(t for _, t, _ in named if t is not None)
+    for name, t, channels in named:
+        if t is None:
+            continue
+        torch_check(t.is_cuda and t.device == edges.device, f'{fn}: {name} must be a CUDA tensor on the device of edges')
+        torch_check(t.dim() == 3 and (channels is None or t.size(2) == channels), f'{fn}: {name} must of size {{batch_size, num_rows, {channels or "feature_dim"}}}')
+        torch_check(t.dtype == first.dtype, f'{fn}: expected every tensor to have the same scalar type')
+        torch_check(t.shape[:2] == first.shape[:2], f'{fn}: {name} must have the batch size and the rows of the other tensor')
+    return _lib.dtype_suffix(first.dtype, fn), first
+
+
+def _batch_items(t):
+    """(tensor, batch stride): items contiguous, the batch stride free (0 for an expanded batch); anything else is copied"""
+    if t.size(0) == 0 or t[0].is_contiguous():
+        return t, (t.stride(0) if t.size(0) > 1 else 0)
+    t = t.contiguous()
+    return t, t.stride(0)
+
+
+def tetmesh_midpoints_forward_cuda(vertices, features, edges, check_edges=True):
+    """vertices (B, V, 3), features (B, V, D) or None, edges (E, 2) of subdivide_tetmesh_cuda -> new_vertices (B, V + E, 3),
+    new_features (B, V + E, D) or None: rows [0, V) are the inputs, row V + e is ``(x[min] + x[max]) * 0.5``; one launch writes
+    both results.  float32 / float64.  ``check_edges``: IndexError for an entry of edges outside [0, V) (skipped by the autograd
+    function, whose edges come straight from subdivide_tetmesh_cuda)."""
+    fn = 'tetmesh_midpoints_forward_cuda'
+    sfx, _ = _tetmesh_midpoints_args(fn, (('vertices', vertices, 3), ('features', features, None)), edges, vertices.size(1),
+                                     check_edges)
+    B, V, E = vertices.size(0), vertices.size(1), edges.size(0)
+    D = features.size(2) if features is not None else 0
+    torch_check(V < 2 ** 32, f'{fn}: more than 2^32 - 1 vertices')
+    dev = vertices.device
+    v, vbs = _batch_items(vertices.detach())
+    f, fbs = _batch_items(features.detach()) if features is not None and D > 0 else (None, 0)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        new_vertices = torch.empty((B, V + E, 3), dtype=v.dtype, device=dev)
+        new_features = torch.empty((B, V + E, D), dtype=v.dtype, device=dev) if features is not None else None
+        if B > 0 and V + E > 0:
+            _lib.check(getattr(lib, f'kamd_tetmesh_midpoints_forward_{sfx}')(
+                _lib.stream_ptr(dev), B, V, E, D, _lib.ptr(v), vbs, _lib.ptr(f), fbs, _lib.ptr(edges), _lib.ptr(new_vertices),
+                _lib.ptr(new_features if f is not None else None)), fn)
+    return new_vertices, new_features
+
+
+def tetmesh_midpoints_backward_cuda(grad_new_vertices, grad_new_features, edges, num_vertices, check_edges=True):
+    """grad_new_vertices (B, V + E, 3) or None, grad_new_features (B, V + E, D) or None (not both), any strides, edges (E, 2)
+    -> grad_vertices (B, V, 3) or None, grad_features (B, V, D) or None: ``g[b, v]`` plus half of ``g[b, V + e]`` for every
+    unique edge that holds v (a self-edge counts twice).  The edges with min = v are one run of the sorted list, summed in
+    order and stored; the halves of the max side are added with native floating-point atomics."""
+    fn = 'tetmesh_midpoints_backward_cuda'
+    torch_check(grad_new_vertices is not None or grad_new_features is not None, f'{fn}: no gradient given')
+    sfx, first = _tetmesh_midpoints_args(fn, (('grad_new_vertices', grad_new_vertices, 3), ('grad_new_features', grad_new_features, None)),
+                                         edges, int(num_vertices), check_edges)
+    B, V, E = first.size(0), int(num_vertices), edges.size(0)
+    torch_check(first.size(1) == V + E, f'{fn}: the gradients must have num_vertices + num_edges rows')
+    torch_check(0 <= V < 2 ** 32, f'{fn}: more than 2^32 - 1 vertices')
+    dev = first.device
+    gv = grad_new_vertices.contiguous() if grad_new_vertices is not None else None
+    gf = grad_new_features.contiguous() if grad_new_features is not None else None
+    D = gf.size(2) if gf is not None else 0
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_vertices = torch.empty((B, V, 3), dtype=first.dtype, device=dev) if gv is not None else None
+        grad_features = torch.empty((B, V, D), dtype=first.dtype, device=dev) if gf is not None else None
+        if B > 0 and V > 0:
+            _lib.check(getattr(lib, f'kamd_tetmesh_midpoints_backward_{sfx}')(
+                _lib.stream_ptr(dev), B, V, E, D, _lib.ptr(gv), _lib.ptr(gf if D > 0 else None), _lib.ptr(edges),
+                _lib.ptr(grad_vertices), _lib.ptr(grad_features if D > 0 else None)), fn)
+    return grad_vertices, grad_features
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
-mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda)
+mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
+                              subdivide_tetmesh_cuda=subdivide_tetmesh_cuda,
+                              tetmesh_midpoints_forward_cuda=tetmesh_midpoints_forward_cuda,
+                              tetmesh_midpoints_backward_cuda=tetmesh_midpoints_backward_cuda)
 conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
                                      marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda)

@@ -65,6 +65,9 @@ SIGNATURES = {
     'kamd_marching_tetrahedra_workspace': (_sz, [_i64, _i64]),
     'kamd_marching_tetrahedra_edges_workspace': (_sz, [_i64, _i64]),
     'kamd_marching_tetrahedra_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    'kamd_subdivide_tetmesh_workspace': (_sz, [_i64, _i64]),
+    'kamd_subdivide_tetmesh_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    'kamd_subdivide_tetmesh_emit': (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
 }
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
@@ -75,6 +78,8 @@ for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_marching_tetrahedra_classify_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_marching_tetrahedra_emit_{_t}'] = (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_marching_tetrahedra_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_midpoints_forward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_midpoints_backward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_packed_rasterize_forward_{_t}'] = (
         _i, [_vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_rasterize_backward_{_t}'] = (

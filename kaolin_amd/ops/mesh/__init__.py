@@ -1,8 +1,10 @@
 """Mesh helpers on the DIB-R path (pure torch): per-face gathers and normals, plus the vertex-set
-subdivision the voxelizer's definition rests on."""
+subdivision the voxelizer's definition rests on; and the tetrahedral-mesh operators of tetmesh.py (subdivide_tetmesh on a HIP
+edge-midpoint pipeline)."""
 import torch
 
-__all__ = ['index_vertices_by_faces', 'face_normals', 'check_sign', 'adjacency_matrix', 'uniform_laplacian']
+__all__ = ['index_vertices_by_faces', 'face_normals', 'check_sign', 'adjacency_matrix', 'uniform_laplacian',
+           'subdivide_tetmesh', 'inverse_vertices_offset']
 
 
 def index_vertices_by_faces(vertices_features, faces):
@@ -167,3 +169,7 @@ def check_sign(verts, faces, points, hash_resolution=512):
     verts, points = verts / scale, points / scale
     one = _unbatched_check_sign_cuda if points.is_cuda else _unbatched_check_sign_torch
     return torch.stack([one(verts[i], faces, points[i]) for i in range(verts.shape[0])])
+
+
+from . import tetmesh  # noqa: E402
+from .tetmesh import subdivide_tetmesh, inverse_vertices_offset  # noqa: E402
