@@ -825,6 +825,57 @@ int kamd_tetmesh_midpoints_backward_f64(void* stream, int64_t B, int64_t V, int6
                                         double* grad_features);
 
 /* ------------------------------------------------------------------------- */
+/* metrics.tetmesh: tetrahedron_volume, equivolume, amips (reference: chains   */
+/* of 10-20 torch kernels, kaolin/metrics/tetmesh.py; csrc/tetmesh_metrics.hip */
+/* has the kernels).  tet_vertices (B,T,4,3): every item's (T,4,3) block is    */
+/* contiguous, items are batch_stride ELEMENTS apart (>= 0; 0 = one item read  */
+/* B times).  16-byte loads are used when the base and the batch stride allow, */
+/* scalar loads otherwise.  Nothing reads back or synchronises: capturable.    */
+/*   volume:     volumes (B,T) = ((A-D).((B-D)x(C-D)))/6; backward takes       */
+/*               grad_volumes (B,T) and fully writes grad_tet_vertices.        */
+/*   equivolume: loss (B) = mean_t |v - mean[0]|^power, power in 1..16; mean   */
+/*               is ONE device element.  backward: grad_loss (B); either of    */
+/*               grad_tet_vertices (B,T,4,3) and grad_mean (1) may be NULL.    */
+/*   amips:      inverse_offset_matrix (B,T,3,3), items inverse_batch_stride   */
+/*               elements apart (0 broadcasts one item); loss (B).  backward:  */
+/*               grad_loss (B); either of grad_tet_vertices and                */
+/*               grad_inverse_offset_matrix (B,T,3,3, per item: the caller     */
+/*               sums a broadcast batch) may be NULL.                          */
+/* The losses (and grad_mean) are reduced without atomics: one double partial  */
+/* per workgroup in `workspace` (kamd_tetmesh_reduce_workspace(B,T) bytes,     */
+/* 8-byte aligned), then a second launch adds them in a fixed order.           */
+/* ------------------------------------------------------------------------- */
+size_t kamd_tetmesh_reduce_workspace(int64_t B, int64_t T);
+int kamd_tetmesh_volume_forward_f32(void* stream, int64_t B, int64_t T, const float* tet_vertices, int64_t batch_stride,
+                                    float* volumes);
+int kamd_tetmesh_volume_backward_f32(void* stream, int64_t B, int64_t T, const float* tet_vertices, int64_t batch_stride,
+                                     const float* grad_volumes, float* grad_tet_vertices);
+int kamd_tetmesh_equivolume_forward_f32(void* stream, int64_t B, int64_t T, const float* tet_vertices, int64_t batch_stride,
+                                        const float* mean, int power, float* loss, void* workspace);
+int kamd_tetmesh_equivolume_backward_f32(void* stream, int64_t B, int64_t T, const float* tet_vertices, int64_t batch_stride,
+                                         const float* mean, int power, const float* grad_loss, float* grad_tet_vertices,
+                                         float* grad_mean, void* workspace);
+int kamd_tetmesh_amips_forward_f32(void* stream, int64_t B, int64_t T, const float* tet_vertices, int64_t batch_stride,
+                                   const float* inverse_offset_matrix, int64_t inverse_batch_stride, float* loss, void* workspace);
+int kamd_tetmesh_amips_backward_f32(void* stream, int64_t B, int64_t T, const float* tet_vertices, int64_t batch_stride,
+                                    const float* inverse_offset_matrix, int64_t inverse_batch_stride, const float* grad_loss,
+                                    float* grad_tet_vertices, float* grad_inverse_offset_matrix);
+int kamd_tetmesh_volume_forward_f64(void* stream, int64_t B, int64_t T, const double* tet_vertices, int64_t batch_stride,
+                                    double* volumes);
+int kamd_tetmesh_volume_backward_f64(void* stream, int64_t B, int64_t T, const double* tet_vertices, int64_t batch_stride,
+                                     const double* grad_volumes, double* grad_tet_vertices);
+int kamd_tetmesh_equivolume_forward_f64(void* stream, int64_t B, int64_t T, const double* tet_vertices, int64_t batch_stride,
+                                        const double* mean, int power, double* loss, void* workspace);
+int kamd_tetmesh_equivolume_backward_f64(void* stream, int64_t B, int64_t T, const double* tet_vertices, int64_t batch_stride,
+                                         const double* mean, int power, const double* grad_loss, double* grad_tet_vertices,
+                                         double* grad_mean, void* workspace);
+int kamd_tetmesh_amips_forward_f64(void* stream, int64_t B, int64_t T, const double* tet_vertices, int64_t batch_stride,
+                                   const double* inverse_offset_matrix, int64_t inverse_batch_stride, double* loss, void* workspace);
+int kamd_tetmesh_amips_backward_f64(void* stream, int64_t B, int64_t T, const double* tet_vertices, int64_t batch_stride,
+                                    const double* inverse_offset_matrix, int64_t inverse_batch_stride, const double* grad_loss,
+                                    double* grad_tet_vertices, double* grad_inverse_offset_matrix);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

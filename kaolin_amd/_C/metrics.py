@@ -250,3 +250,163 @@ def unbatched_triangle_distance_backward_cuda(grad_dist, points, face_vertices, 
             _lib.ptr(face_vertices), _lib.ptr(face_idx), _lib.ptr(dist_type), _lib.ptr(grad_points),
             _lib.ptr(grad_face_vertices))
     _lib.check(st, fn)
+
+
+# ---- metrics.tetmesh (csrc/tetmesh_metrics.hip).  Not part of the reference's ``kaolin._C``: it evaluates these three losses as
+# chains of torch kernels (kaolin/metrics/tetmesh.py).  Nothing below reads back or synchronises: the operators capture into a graph.
+def _batch_items(t):
+    """(tensor, batch stride in elements): every item contiguous, the batch stride free (0 for an expanded batch); anything
+    else is copied"""
+    if t.size(0) == 0 or t[0].is_contiguous():
+        return t, (t.stride(0) if t.size(0) > 1 else 0)
+    t = t.contiguous()
+    return t, t.stride(0)
+
+
+def _tetmesh_args(fn, tet_vertices, others=()):
+    """tet_vertices (B, T, 4, 3) float32 / float64 on a GPU; others: ((name, tensor or None, shape), ...) of the same dtype and
+    device -> (suffix, B, T)"""
+    torch_check(tet_vertices.is_cuda, f'{fn}: tet_vertices must be a CUDA tensor')
+    torch_check(tet_vertices.dim() == 4 and tet_vertices.shape[2:] == (4, 3),
+                f'{fn}: tet_vertices must of size {{batch_size, num_tetrahedrons, 4, 3}}')
+    sfx = _lib.dtype_suffix(tet_vertices.dtype, fn)
+    for name, t, shape in others:
+        if t is None:
+            continue
+        torch_check(t.is_cuda and t.device == tet_vertices.device, f'{fn}: {name} must be a CUDA tensor on the device of tet_vertices')
+        torch_check(t.dtype == tet_vertices.dtype, f'{fn}: expected {name} to have the scalar type of tet_vertices')
+        torch_check(tuple(t.shape) == tuple(shape), f'{fn}: {name} must of size {{{", ".join(str(s) for s in shape)}}}')
+    return sfx, tet_vertices.size(0), tet_vertices.size(1)
+
+
+def _tetmesh_workspace(lib, B, T, device):
+    return _lib.workspace(lib.kamd_tetmesh_reduce_workspace(B, T), device)
+
+
+def tetmesh_volume_forward_cuda(tet_vertices):
+    """tet_vertices (B, T, 4, 3) -> volumes (B, T): ``((A - D) . ((B - D) x (C - D))) / 6``, signed."""
+    fn = 'tetmesh_volume_forward_cuda'
+    sfx, B, T = _tetmesh_args(fn, tet_vertices)
+    dev = tet_vertices.device
+    tv, bs = _batch_items(tet_vertices.detach())
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        volumes = torch.empty((B, T), dtype=tv.dtype, device=dev)
+        if B > 0 and T > 0:
+            _lib.check(getattr(lib, f'kamd_tetmesh_volume_forward_{sfx}')(
+                _lib.stream_ptr(dev), B, T, _lib.ptr(tv), bs, _lib.ptr(volumes)), fn)
+    return volumes
+
+
+def tetmesh_volume_backward_cuda(grad_volumes, tet_vertices):
+    """grad_volumes (B, T), any strides; tet_vertices (B, T, 4, 3) -> grad_tet_vertices (B, T, 4, 3), recomputed from the input."""
+    fn = 'tetmesh_volume_backward_cuda'
+    sfx, B, T = _tetmesh_args(fn, tet_vertices, (('grad_volumes', grad_volumes, (tet_vertices.size(0), tet_vertices.size(1))),))
+    dev = tet_vertices.device
+    tv, bs = _batch_items(tet_vertices.detach())
+    g = grad_volumes.contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad = torch.empty((B, T, 4, 3), dtype=tv.dtype, device=dev)
+        if B > 0 and T > 0:
+            _lib.check(getattr(lib, f'kamd_tetmesh_volume_backward_{sfx}')(
+                _lib.stream_ptr(dev), B, T, _lib.ptr(tv), bs, _lib.ptr(g), _lib.ptr(grad)), fn)
+    return grad
+
+
+def _check_power(fn, power):
+    torch_check(isinstance(power, int) and not isinstance(power, bool) and 1 <= power <= 16, f'{fn}: pow must be an int in [1, 16]')
+
+
+def tetmesh_equivolume_forward_cuda(tet_vertices, mean, power):
+    """tet_vertices (B, T, 4, 3), T >= 1; mean: ONE element; power: int in [1, 16] -> loss (B, 1): the mean over the tets of
+    ``|volume - mean| ** power``.  Two launches: a partial per workgroup, then their sum in a fixed order (no atomics)."""
+    fn = 'tetmesh_equivolume_forward_cuda'
+    sfx, B, T = _tetmesh_args(fn, tet_vertices, (('mean', mean, (1,) * mean.dim()),))
+    _check_power(fn, power)
+    torch_check(T > 0, f'{fn}: no tetrahedrons')
+    dev = tet_vertices.device
+    tv, bs = _batch_items(tet_vertices.detach())
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        loss = torch.empty((B, 1), dtype=tv.dtype, device=dev)
+        if B > 0:
+            ws = _tetmesh_workspace(lib, B, T, dev)
+            _lib.check(getattr(lib, f'kamd_tetmesh_equivolume_forward_{sfx}')(
+                _lib.stream_ptr(dev), B, T, _lib.ptr(tv), bs, _lib.ptr(mean.detach()), power, _lib.ptr(loss), _lib.ptr(ws)), fn)
+    return loss
+
+
+def tetmesh_equivolume_backward_cuda(grad_loss, tet_vertices, mean, power, need_tet_vertices=True, need_mean=True):
+    """grad_loss (B, 1), any strides -> (grad_tet_vertices (B, T, 4, 3) or None, grad_mean of mean's shape or None); each is
+    computed only when asked for.  At ``volume == mean`` the term is 0, as ``torch.abs``'s gradient."""
+    fn = 'tetmesh_equivolume_backward_cuda'
+    sfx, B, T = _tetmesh_args(fn, tet_vertices, (('mean', mean, (1,) * mean.dim()), ('grad_loss', grad_loss, (tet_vertices.size(0), 1))))
+    _check_power(fn, power)
+    torch_check(T > 0, f'{fn}: no tetrahedrons')
+    dev = tet_vertices.device
+    tv, bs = _batch_items(tet_vertices.detach())
+    g = grad_loss.contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_tv = torch.empty((B, T, 4, 3), dtype=tv.dtype, device=dev) if need_tet_vertices else None
+        grad_mean = torch.zeros(mean.shape, dtype=tv.dtype, device=dev) if need_mean else None
+        if B > 0 and (need_tet_vertices or need_mean):
+            ws = _tetmesh_workspace(lib, B, T, dev) if need_mean else None
+            _lib.check(getattr(lib, f'kamd_tetmesh_equivolume_backward_{sfx}')(
+                _lib.stream_ptr(dev), B, T, _lib.ptr(tv), bs, _lib.ptr(mean.detach()), power, _lib.ptr(g), _lib.ptr(grad_tv),
+                _lib.ptr(grad_mean), _lib.ptr(ws)), fn)
+    return grad_tv, grad_mean
+
+
+def _inverse_items(fn, tet_vertices, inverse_offset_matrix):
+    B, T = tet_vertices.size(0), tet_vertices.size(1)
+    torch_check(inverse_offset_matrix.dim() == 4 and inverse_offset_matrix.size(0) in (1, B),
+                f'{fn}: inverse_offset_matrix must of size {{batch_size or 1, num_tetrahedrons, 3, 3}}')
+    inv, ibs = _batch_items(inverse_offset_matrix.detach())
+    return inv, (ibs if inv.size(0) > 1 else 0)     # (a batch of one against B > 1 is read B times)
+
+
+def tetmesh_amips_forward_cuda(tet_vertices, inverse_offset_matrix):
+    """tet_vertices (B, T, 4, 3), T >= 1; inverse_offset_matrix (B or 1, T, 3, 3) -> loss (B, 1): the mean over the tets of
+    ``tr(J J^T) / (det(J)^2 + 1e-10)^(1/3) * (det(J) >= 0)``, J = (rows B - A, C - A, D - A) M.  Two launches, no atomics."""
+    fn = 'tetmesh_amips_forward_cuda'
+    shape = (inverse_offset_matrix.size(0) if inverse_offset_matrix.dim() else 0, tet_vertices.size(1), 3, 3)
+    sfx, B, T = _tetmesh_args(fn, tet_vertices, (('inverse_offset_matrix', inverse_offset_matrix, shape),))
+    torch_check(T > 0, f'{fn}: no tetrahedrons')
+    dev = tet_vertices.device
+    tv, bs = _batch_items(tet_vertices.detach())
+    inv, ibs = _inverse_items(fn, tet_vertices, inverse_offset_matrix)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        loss = torch.empty((B, 1), dtype=tv.dtype, device=dev)
+        if B > 0:
+            ws = _tetmesh_workspace(lib, B, T, dev)
+            _lib.check(getattr(lib, f'kamd_tetmesh_amips_forward_{sfx}')(
+                _lib.stream_ptr(dev), B, T, _lib.ptr(tv), bs, _lib.ptr(inv), ibs, _lib.ptr(loss), _lib.ptr(ws)), fn)
+    return loss
+
+
+def tetmesh_amips_backward_cuda(grad_loss, tet_vertices, inverse_offset_matrix, need_tet_vertices=True, need_inverse=True):
+    """grad_loss (B, 1), any strides -> (grad_tet_vertices (B, T, 4, 3) or None, grad_inverse_offset_matrix of the matrix' shape
+    or None); each is computed only when asked for.  A matrix batch of one against B > 1 gets the sum over the items."""
+    fn = 'tetmesh_amips_backward_cuda'
+    shape = (inverse_offset_matrix.size(0) if inverse_offset_matrix.dim() else 0, tet_vertices.size(1), 3, 3)
+    sfx, B, T = _tetmesh_args(fn, tet_vertices, (('inverse_offset_matrix', inverse_offset_matrix, shape),
+                                                 ('grad_loss', grad_loss, (tet_vertices.size(0), 1))))
+    torch_check(T > 0, f'{fn}: no tetrahedrons')
+    dev = tet_vertices.device
+    tv, bs = _batch_items(tet_vertices.detach())
+    inv, ibs = _inverse_items(fn, tet_vertices, inverse_offset_matrix)
+    g = grad_loss.contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_tv = torch.empty((B, T, 4, 3), dtype=tv.dtype, device=dev) if need_tet_vertices else None
+        grad_inv = torch.empty((B, T, 3, 3), dtype=tv.dtype, device=dev) if need_inverse else None
+        if B > 0 and (need_tet_vertices or need_inverse):
+            _lib.check(getattr(lib, f'kamd_tetmesh_amips_backward_{sfx}')(
+                _lib.stream_ptr(dev), B, T, _lib.ptr(tv), bs, _lib.ptr(inv), ibs, _lib.ptr(g), _lib.ptr(grad_tv),
+                _lib.ptr(grad_inv)), fn)
+        if grad_inv is not None and inverse_offset_matrix.size(0) != B:
+            grad_inv = grad_inv.sum(dim=0, keepdim=True)
+    return grad_tv, grad_inv

@@ -8,6 +8,7 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
     kaolin_amd.ops.mesh         subdivide_tetmesh (HIP edge-midpoint pipeline), inverse_vertices_offset, check_sign
     kaolin_amd.ops.voxelgrid    fill (HIP flood fill over bit grids), downsample, extract_surface, extract_odms, project_odms
     kaolin_amd.metrics.voxelgrid  iou
+    kaolin_amd.metrics.tetmesh  tetrahedron_volume, equivolume, amips (fused HIP kernels, atomic-free reductions)
     kaolin_amd.render.lighting  spherical-gaussian (HIP reduced inner product) and spherical-harmonic shading
     kaolin_amd._C               the 8 operator bindings of ``kaolin._C`` on this path
     kaolin_amd.distributed      batch/view sharding over RCCL (new; the reference has none)

@@ -68,6 +68,7 @@ SIGNATURES = {
     'kamd_subdivide_tetmesh_workspace': (_sz, [_i64, _i64]),
     'kamd_subdivide_tetmesh_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
     'kamd_subdivide_tetmesh_emit': (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    'kamd_tetmesh_reduce_workspace': (_sz, [_i64, _i64]),
 }
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
@@ -80,6 +81,12 @@ for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_marching_tetrahedra_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_tetmesh_midpoints_forward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp])
     SIGNATURES[f'kamd_tetmesh_midpoints_backward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_volume_forward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp])
+    SIGNATURES[f'kamd_tetmesh_volume_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_equivolume_forward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_equivolume_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_amips_forward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp])
+    SIGNATURES[f'kamd_tetmesh_amips_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp])
     SIGNATURES[f'kamd_packed_rasterize_forward_{_t}'] = (
         _i, [_vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_rasterize_backward_{_t}'] = (
