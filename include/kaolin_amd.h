@@ -825,6 +825,40 @@ int kamd_tetmesh_midpoints_backward_f64(void* stream, int64_t B, int64_t V, int6
                                         double* grad_features);
 
 /* ------------------------------------------------------------------------- */
+/* ops.conversions.voxelgrids_to_cubic_meshes (reference: conv3d, nonzero,     */
+/* repeat_interleave and a torch.unique(dim=0) per item, kaolin/ops/           */
+/* conversions/voxelgrid.py; csrc/cubic_meshes.hip has the sort-free pipeline). */
+/* voxelgrids: (B,X,Y,Z) with ELEMENT strides (any layout, read in place);     */
+/* u8 also serves bool, f16 is the raw half.  (X+1)(Y+1)(Z+1) < 2^31 per item. */
+/* One `workspace` of kamd_cubic_meshes_workspace(B,X,Y,Z) bytes (host         */
+/* arithmetic; 0 = an empty batch or a lattice beyond the 32-bit range),       */
+/* 16-byte aligned, carries the state from step to step:                       */
+/*   1. classify_*: a code byte per lattice point and four counts per          */
+/*      workgroup (vertices, faces of axis 0, 1, 2).                           */
+/*   2. scan: exclusive scans of the counts; host_totals (B,4) uint32 <- per   */
+/*      item the vertices and the faces of axis 0, 1, 2.  Reads them back:     */
+/*      SYNCHRONISES the stream (not capturable in a graph).                   */
+/*   3. emit_vertices: verts (sum V_b, 3) float32, the items one after the     */
+/*      other, lattice coordinates in lexicographic order.                     */
+/*   4. emit_faces: faces int64, the items one after the other, ids local to   */
+/*      the item: (sum N_b, 4) quads, or with is_trimesh (2 sum N_b, 3), item  */
+/*      b holding corners [0,3,1] of its quads in rows [0,N_b) and [2,1,3] in  */
+/*      [N_b, 2 N_b).  Needs step 3 (the rank of every vertex).                */
+/* Steps 3 and 4 are skipped by the caller when nothing is to be written.      */
+/* ------------------------------------------------------------------------- */
+size_t kamd_cubic_meshes_workspace(int64_t B, int X, int Y, int Z);
+int kamd_cubic_meshes_classify_u8(void* stream, int64_t B, int X, int Y, int Z, const uint8_t* voxelgrids, int64_t stride_n,
+                                  int64_t stride_x, int64_t stride_y, int64_t stride_z, void* workspace);
+int kamd_cubic_meshes_classify_f16(void* stream, int64_t B, int X, int Y, int Z, const void* voxelgrids, int64_t stride_n,
+                                   int64_t stride_x, int64_t stride_y, int64_t stride_z, void* workspace);
+int kamd_cubic_meshes_classify_f32(void* stream, int64_t B, int X, int Y, int Z, const float* voxelgrids, int64_t stride_n,
+                                   int64_t stride_x, int64_t stride_y, int64_t stride_z, void* workspace);
+int kamd_cubic_meshes_scan(void* stream, int64_t B, int X, int Y, int Z, void* workspace, uint32_t* host_totals);
+int kamd_cubic_meshes_emit_vertices(void* stream, int64_t B, int X, int Y, int Z, void* workspace, float* verts);
+int kamd_cubic_meshes_emit_faces(void* stream, int64_t B, int X, int Y, int Z, const void* workspace, int is_trimesh,
+                                 int64_t* faces);
+
+/* ------------------------------------------------------------------------- */
 /* metrics.tetmesh: tetrahedron_volume, equivolume, amips (reference: chains   */
 /* of 10-20 torch kernels, kaolin/metrics/tetmesh.py; csrc/tetmesh_metrics.hip */
 /* has the kernels).  tet_vertices (B,T,4,3): every item's (T,4,3) block is    */

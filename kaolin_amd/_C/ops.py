@@ -188,6 +188,55 @@ def voxelgrid_fill_cuda(voxelgrids, stats=None):
     return out
 
 
+_CUBIC_SUFFIX = {torch.bool: 'u8', torch.uint8: 'u8', torch.float16: 'f16', torch.float32: 'f32'}
+
+
+def voxelgrids_to_cubic_meshes_cuda(voxelgrids, is_trimesh=True):
+    """kaolin.ops.conversions.voxelgrids_to_cubic_meshes on the sort-free HIP pipeline of csrc/cubic_meshes.hip (the reference has
+    no ``_C`` operator here: its voxelgrid.py is conv3d, nonzero and a torch.unique(dim=0) per item).  voxelgrids (B, X, Y, Z),
+    any strides; bool / uint8 / half / float are read in place, any other dtype is cast once with ``.float()`` as the reference
+    does -> (verts, faces): two lists of B tensors, verts[b] (V_b, 3) float32 and faces[b] (2 N_b, 3) or (N_b, 4) int64, views of
+    one vertex buffer and one face buffer for the batch.  Result sizes depend on the data: the host reads the B x 4 totals
+    once, so the call synchronises the current stream and cannot be captured in a graph (like the reference, whose nonzero and
+    torch.unique synchronise)."""
+    fn = 'voxelgrids_to_cubic_meshes_cuda'
+    torch_check(voxelgrids.is_cuda, f'{fn}: voxelgrids must be a CUDA tensor')
+    torch_check(voxelgrids.dim() == 4, f'{fn}: voxelgrids must of size {{batch_size, X, Y, Z}}')
+    v = voxelgrids.detach()
+    sfx = _CUBIC_SUFFIX.get(v.dtype)
+    if sfx is None:
+        v = v.float()
+        sfx = 'f32'
+    B, X, Y, Z = v.shape
+    width = 3 if is_trimesh else 4
+    dev = v.device
+    if B == 0:
+        return [], []
+    torch_check((X + 1) * (Y + 1) * (Z + 1) < 2 ** 31,
+                f'{fn}: the lattice (X + 1)(Y + 1)(Z + 1) = {(X + 1) * (Y + 1) * (Z + 1)} of one item must stay below 2^31')
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    totals = None
+    with _lib.on_device(dev):
+        if v.numel() > 0:
+            nbytes = lib.kamd_cubic_meshes_workspace(B, X, Y, Z)
+            torch_check(nbytes > 0, f'{fn}: a batch of {B} grids of {X} x {Y} x {Z} is beyond the launch range')
+            ws = _lib.workspace(nbytes, dev)
+            _lib.check(getattr(lib, f'kamd_cubic_meshes_classify_{sfx}')(
+                sp, B, X, Y, Z, _lib.ptr(v), *v.stride(), _lib.ptr(ws)), fn)
+            host = (ctypes.c_uint32 * (4 * B))()
+            _lib.check(lib.kamd_cubic_meshes_scan(sp, B, X, Y, Z, _lib.ptr(ws), ctypes.cast(host, ctypes.c_void_p)), fn)
+            totals = list(host)                                # data-dependent sizes: the one host read
+        nv = [totals[4 * b] for b in range(B)] if totals else [0] * B
+        nq = [sum(totals[4 * b + 1:4 * b + 4]) for b in range(B)] if totals else [0] * B
+        verts = torch.empty((sum(nv), 3), dtype=torch.float32, device=dev)
+        faces = torch.empty(((2 if is_trimesh else 1) * sum(nq), width), dtype=torch.long, device=dev)
+        if faces.numel() > 0:
+            _lib.check(lib.kamd_cubic_meshes_emit_vertices(sp, B, X, Y, Z, _lib.ptr(ws), _lib.ptr(verts)), fn)
+            _lib.check(lib.kamd_cubic_meshes_emit_faces(sp, B, X, Y, Z, _lib.ptr(ws), int(bool(is_trimesh)), _lib.ptr(faces)), fn)
+    return (list(torch.split(verts, nv)), list(torch.split(faces, [(2 if is_trimesh else 1) * n for n in nq])))
+
+
 def check_tets_in_range(tets, num_vertices, fn='marching_tetrahedra'):
     """tets (T, 4) of an integer dtype on any device: raises IndexError when an entry lies outside [0, num_vertices).  Pure
     torch (one min / max pass and one host read); called before any kernel sees the ids -- an id out of range would make the
@@ -406,4 +455,5 @@ mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_in
                               tetmesh_midpoints_forward_cuda=tetmesh_midpoints_forward_cuda,
                               tetmesh_midpoints_backward_cuda=tetmesh_midpoints_backward_cuda)
 conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
-                                     marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda)
+                                     marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda,
+                                     voxelgrids_to_cubic_meshes_cuda=voxelgrids_to_cubic_meshes_cuda)

@@ -69,12 +69,18 @@ SIGNATURES = {
     'kamd_subdivide_tetmesh_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
     'kamd_subdivide_tetmesh_emit': (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     'kamd_tetmesh_reduce_workspace': (_sz, [_i64, _i64]),
+    'kamd_cubic_meshes_workspace': (_sz, [_i64, _i, _i, _i]),
+    'kamd_cubic_meshes_scan': (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
+    'kamd_cubic_meshes_emit_vertices': (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
+    'kamd_cubic_meshes_emit_faces': (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _vp]),
 }
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_sided_distance_backward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp])
 for _t in ('u8', 'i32', 'i64', 'f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_voxelgrid_fill_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp])
+for _t in ('u8', 'f16', 'f32'):
+    SIGNATURES[f'kamd_cubic_meshes_classify_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _vp])
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_marching_tetrahedra_classify_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_marching_tetrahedra_emit_{_t}'] = (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp])

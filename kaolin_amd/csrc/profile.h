@@ -21,6 +21,7 @@ enum KernelId {
   K_VOX_VERTICES, K_VOX_FACES, K_MEMSET, K_PV_FORWARD, K_PV_BACKWARD, K_MESH_INTERSECTION,
   K_DEFTET_FORWARD, K_DEFTET_SORT, K_DEFTET_BACKWARD, K_SPC_STAGE, K_SPC_BUILD, K_MASK_IOU, K_TEXTURE_MAPPING,
   K_WEIGHTED_SUM, K_SOFT_SELECT_ROUNDS, K_VOXFILL_PACK, K_VOXFILL_PASS, K_VOXFILL_UNPACK,
+  K_CUBIC_CLASSIFY, K_CUBIC_SCAN, K_CUBIC_VERTICES, K_CUBIC_FACES,
   K_NUM
 };
 

@@ -16,7 +16,8 @@ const char* const kNames[K_NUM] = {
     "deftet_forward(pixel sort + search)", "deftet_sort_interp_kernel", "deftet_backward_kernel",
     "mesh_to_spc_stage(count|emit)", "mesh_to_spc_build(sort + unique + octree + results)", "mask_iou_kernels",
     "texture_mapping_kernel", "weighted_sum2_kernels", "soft_select_rounds_kernel",
-    "vf_pack_kernel", "vf_pass_kernel", "vf_unpack_kernel"};
+    "vf_pack_kernel", "vf_pass_kernel", "vf_unpack_kernel",
+    "cm_classify_kernel", "cm_scan(scan + bases)", "cm_vertices_kernel", "cm_faces_kernel"};
 struct Pending {
   int id;
   hipEvent_t start, stop;

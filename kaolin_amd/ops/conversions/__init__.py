@@ -2,3 +2,5 @@ from .trianglemesh import trianglemeshes_to_voxelgrids, unbatched_mesh_to_spc  #
 from . import trianglemesh  # noqa: F401
 from .tetmesh import marching_tetrahedra  # noqa: F401
 from . import tetmesh  # noqa: F401
+from .voxelgrid import voxelgrids_to_cubic_meshes  # noqa: F401
+from . import voxelgrid  # noqa: F401
