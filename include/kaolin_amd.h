@@ -825,6 +825,61 @@ int kamd_tetmesh_midpoints_backward_f64(void* stream, int64_t B, int64_t V, int6
                                         double* grad_features);
 
 /* ------------------------------------------------------------------------- */
+/* ops.mesh.subdivide_trianglemesh: one iteration of Loop subdivision with a   */
+/* per-vertex alpha (reference: two torch.unique, a sparse bmm, two sorts and  */
+/* a chain of gathers, kaolin/ops/mesh/trianglemesh.py; csrc/                  */
+/* subdivide_trianglemesh.hip has the pipeline and the rules).  faces: (F,3)   */
+/* int64 contiguous, every id in [0,V) (the shim raises before it gets here),  */
+/* V < 2^32.  Topology, once per iteration:                                    */
+/*   1. edges: workspace <- the 3 F keys min << 32 | max, sorted, and the      */
+/*      unique ones; *host_num_edges <- E.  Reads E back: SYNCHRONISES the     */
+/*      stream (not capturable in a graph).                                    */
+/*   2. emit, all fully written except `opp`: edges (E,2) int64 = the          */
+/*      (min,max) pairs in ascending order; new_faces (4 F,3) int64, four rows */
+/*      per face, edge e being vertex V + e; count (E) int32 = face slots per  */
+/*      edge; opp (E,2) int64 = the opposite corners of the first two slots    */
+/*      claimed (valid where count == 2; read there only); tlist (E,2) int64 = */
+/*      (min end, edge id) in ascending (max,min) order; runs (V+1,2) int64 =  */
+/*      where the runs of vertex v start in edges / tlist; valence (V) int32.  */
+/*      The int64 results and the workspace are 16-byte aligned.               */
+/* The workspace query is host arithmetic; 0 = nothing to do (F = 0).          */
+/* Values, the whole batch per call; vertices (B,V,3) and alpha (B,V) with     */
+/* contiguous items `*_batch_stride` elements apart (0: an expanded batch);    */
+/* alpha NULL = the Loop weights from the valences.  The topology tensors are  */
+/* gathered by UNCHECKED: they come from step 2.                               */
+/*   forward: new_vertices (B,V+E,3), new_alpha (B,V+E; NULL with alpha NULL)  */
+/*      contiguous, fully written by one launch; no floating-point atomics.    */
+/*   backward: grad_new_vertices (B,V+E,3), grad_new_alpha (B,V+E) or NULL;    */
+/*      grad_vertices (B,V,3), grad_alpha (B,V) or NULL, fully written: a      */
+/*      gather with plain stores, then fp atomic adds of the opposite-corner   */
+/*      terms.                                                                 */
+/* ------------------------------------------------------------------------- */
+size_t kamd_subdivide_trianglemesh_workspace(int64_t F, int64_t V);
+int kamd_subdivide_trianglemesh_edges(void* stream, int64_t F, int64_t V, const int64_t* faces, void* workspace,
+                                      int64_t* host_num_edges);
+int kamd_subdivide_trianglemesh_emit(void* stream, int64_t F, int64_t V, const int64_t* faces, void* workspace, int64_t num_edges,
+                                     int64_t* edges, int64_t* new_faces, int32_t* count, int64_t* opp, int64_t* tlist, int64_t* runs,
+                                     int32_t* valence);
+int kamd_trianglemesh_loop_forward_f32(void* stream, int64_t B, int64_t V, int64_t E, const float* vertices,
+                                       int64_t vertices_batch_stride, const float* alpha, int64_t alpha_batch_stride,
+                                       const int64_t* edges, const int32_t* count, const int64_t* opp, const int64_t* tlist,
+                                       const int64_t* runs, const int32_t* valence, float* new_vertices, float* new_alpha);
+int kamd_trianglemesh_loop_forward_f64(void* stream, int64_t B, int64_t V, int64_t E, const double* vertices,
+                                       int64_t vertices_batch_stride, const double* alpha, int64_t alpha_batch_stride,
+                                       const int64_t* edges, const int32_t* count, const int64_t* opp, const int64_t* tlist,
+                                       const int64_t* runs, const int32_t* valence, double* new_vertices, double* new_alpha);
+int kamd_trianglemesh_loop_backward_f32(void* stream, int64_t B, int64_t V, int64_t E, const float* grad_new_vertices,
+                                        const float* grad_new_alpha, const float* vertices, int64_t vertices_batch_stride,
+                                        const float* alpha, int64_t alpha_batch_stride, const int64_t* edges, const int32_t* count,
+                                        const int64_t* opp, const int64_t* tlist, const int64_t* runs, const int32_t* valence,
+                                        float* grad_vertices, float* grad_alpha);
+int kamd_trianglemesh_loop_backward_f64(void* stream, int64_t B, int64_t V, int64_t E, const double* grad_new_vertices,
+                                        const double* grad_new_alpha, const double* vertices, int64_t vertices_batch_stride,
+                                        const double* alpha, int64_t alpha_batch_stride, const int64_t* edges, const int32_t* count,
+                                        const int64_t* opp, const int64_t* tlist, const int64_t* runs, const int32_t* valence,
+                                        double* grad_vertices, double* grad_alpha);
+
+/* ------------------------------------------------------------------------- */
 /* ops.conversions.voxelgrids_to_cubic_meshes (reference: conv3d, nonzero,     */
 /* repeat_interleave and a torch.unique(dim=0) per item, kaolin/ops/           */
 /* conversions/voxelgrid.py; csrc/cubic_meshes.hip has the sort-free pipeline). */

@@ -448,9 +448,136 @@ def tetmesh_midpoints_backward_cuda(grad_new_vertices, grad_new_features, edges,
     return grad_vertices, grad_features
 
 
+def check_faces_in_range(faces, num_vertices, fn='subdivide_trianglemesh'):
+    """faces (F, 3) of an integer dtype on any device: raises IndexError when an entry lies outside [0, num_vertices).  Pure
+    torch (one min / max pass and one host read); called before any kernel sees the ids -- an id out of range would make the
+    HIP path read outside its buffers."""
+    torch_check(faces.dim() == 2 and faces.size(1) == 3, f'{fn}: faces must of size {{num_faces, 3}}')
+    torch_check(not faces.dtype.is_floating_point and not faces.dtype.is_complex, f'{fn}: faces must be of an integer type')
+    if faces.numel() == 0:
+        return
+    lo, hi = torch.stack(torch.aminmax(faces)).tolist()
+    if lo < 0 or hi >= num_vertices:
+        raise IndexError(f'{fn}: faces hold the index {lo if lo < 0 else hi}, outside [0, num_vertices = {num_vertices})')
+
+
+# the topology tensors of one Loop iteration, in the order the C ABI takes them
+LOOP_TOPOLOGY = ('edges', 'count', 'opp', 'tlist', 'runs', 'valence')
+
+
+def subdivide_trianglemesh_cuda(faces, num_vertices, check_faces=True):
+    """The topology of one iteration of kaolin.ops.mesh.subdivide_trianglemesh on the HIP pipeline of
+    csrc/subdivide_trianglemesh.hip (the reference has no ``_C`` operator here).  faces (F, 3) int64, F > 0, ids in
+    [0, num_vertices) -> new_faces (4 F, 3) int64 and the tuple LOOP_TOPOLOGY: edges (E, 2) int64, the unique (min, max) edges in
+    ascending order, edge e being the new vertex ``num_vertices + e``; count (E) int32, the face slots per edge; opp (E, 2) int64,
+    two opposite corners (meaningful where count == 2); tlist (E, 2) int64, (min end, edge id) in ascending (max, min) order; runs
+    (V + 1, 2) int64, the starts of every vertex's runs in edges and tlist; valence (V) int32.  The host reads E back: the call
+    synchronises the current stream once and cannot be captured in a graph (like the reference, whose torch.unique synchronises).
+    ``check_faces``: IndexError for an entry of faces outside [0, num_vertices) -- the kernels gather by them unchecked (skipped
+    by the public function, which has checked the first iteration's faces and makes the later ones itself)."""
+    fn = 'subdivide_trianglemesh_cuda'
+    V = int(num_vertices)
+    if check_faces:
+        check_faces_in_range(faces, V, fn)
+    torch_check(faces.dim() == 2 and faces.size(1) == 3, f'{fn}: faces must of size {{num_faces, 3}}')
+    torch_check(faces.is_cuda, f'{fn}: faces must be a CUDA tensor')
+    torch_check(faces.dtype == torch.long, f'{fn}: faces must be long')
+    torch_check(0 < V < 2 ** 32, f'{fn}: the number of vertices must be in [1, 2^32)')
+    dev, F = faces.device, faces.size(0)
+    torch_check(F > 0, f'{fn}: no faces')
+    f = faces.contiguous()
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(lib.kamd_subdivide_trianglemesh_workspace(F, V), dev)
+        torch_check(ws is not None, f'{fn}: {F} faces are more than the pipeline takes')
+        count = ctypes.c_int64(0)
+        _lib.check(lib.kamd_subdivide_trianglemesh_edges(sp, F, V, _lib.ptr(f), _lib.ptr(ws),
+                                                         ctypes.cast(ctypes.pointer(count), ctypes.c_void_p)), fn)
+        E = count.value                                        # data-dependent size: the one host read
+        new_faces = torch.empty((4 * F, 3), dtype=torch.long, device=dev)
+        topo = (torch.empty((E, 2), dtype=torch.long, device=dev), torch.empty(E, dtype=torch.int32, device=dev),
+                torch.empty((E, 2), dtype=torch.long, device=dev), torch.empty((E, 2), dtype=torch.long, device=dev),
+                torch.empty((V + 1, 2), dtype=torch.long, device=dev), torch.empty(V, dtype=torch.int32, device=dev))
+        for t in (ws, new_faces) + topo:
+            torch_check(t.data_ptr() % 16 == 0, f'{fn}: an allocation is not 16-byte aligned')
+        _lib.check(lib.kamd_subdivide_trianglemesh_emit(sp, F, V, _lib.ptr(f), _lib.ptr(ws), E, _lib.ptr(topo[0]), _lib.ptr(new_faces),
+                                                        *(_lib.ptr(t) for t in topo[1:])), fn)
+    return new_faces, topo
+
+
+def _loop_args(fn, vertices, alpha, topo, rows):
+    """vertices-like (B, rows, 3) and alpha-like (B, rows) or None, of one float32 / float64 dtype, on the device of the topology
+    tuple of subdivide_trianglemesh_cuda -> (dtype suffix, V, E)"""
+    torch_check(isinstance(topo, (tuple, list)) and len(topo) == len(LOOP_TOPOLOGY), f'{fn}: topo must be the tuple {LOOP_TOPOLOGY}')
+    edges, count, opp, tlist, runs, valence = topo
+    V, E = valence.size(0), edges.size(0)
+    for name, t, shape, dtype in (('edges', edges, (E, 2), torch.long), ('count', count, (E,), torch.int32), ('opp', opp, (E, 2), torch.long),
+                                  ('tlist', tlist, (E, 2), torch.long), ('runs', runs, (V + 1, 2), torch.long),
+                                  ('valence', valence, (V,), torch.int32)):
+        torch_check(t.is_cuda and t.device == edges.device and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                    f'{fn}: {name} must be a contiguous CUDA {dtype} tensor of size {shape}')
+        torch_check(t.data_ptr() % 16 == 0, f'{fn}: {name} must be 16-byte aligned')
+    torch_check(0 < V < 2 ** 32, f'{fn}: the number of vertices must be in [1, 2^32)')
+    torch_check(vertices.is_cuda and vertices.device == edges.device, f'{fn}: expected a CUDA tensor on the device of the topology')
+    torch_check(vertices.dim() == 3 and tuple(vertices.shape[1:]) == (rows(V, E), 3), f'{fn}: expected size {{batch_size, {rows(V, E)}, 3}}')
+    if alpha is not None:
+        torch_check(alpha.is_cuda and alpha.device == edges.device and alpha.dtype == vertices.dtype,
+                    f'{fn}: expected every tensor to have the same device and scalar type')
+        torch_check(tuple(alpha.shape) == (vertices.size(0), rows(V, E)), f'{fn}: expected size {{batch_size, {rows(V, E)}}}')
+    return _lib.dtype_suffix(vertices.dtype, fn), V, E
+
+
+def trianglemesh_loop_forward_cuda(vertices, alpha, topo):
+    """vertices (B, V, 3), alpha (B, V) or None (the Loop weights from the valences), topo of subdivide_trianglemesh_cuda ->
+    new_vertices (B, V + E, 3), new_alpha (B, V + E) or None.  One launch, gathers only: two calls give the same bits."""
+    fn = 'trianglemesh_loop_forward_cuda'
+    sfx, V, E = _loop_args(fn, vertices, alpha, topo, lambda V, E: V)
+    B, dev = vertices.size(0), vertices.device
+    v, vbs = _batch_items(vertices.detach())
+    a, abs_ = _batch_items(alpha.detach()) if alpha is not None else (None, 0)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        new_vertices = torch.empty((B, V + E, 3), dtype=v.dtype, device=dev)
+        new_alpha = torch.empty((B, V + E), dtype=v.dtype, device=dev) if a is not None else None
+        if B > 0:
+            _lib.check(getattr(lib, f'kamd_trianglemesh_loop_forward_{sfx}')(
+                _lib.stream_ptr(dev), B, V, E, _lib.ptr(v), vbs, _lib.ptr(a), abs_, *(_lib.ptr(t) for t in topo),
+                _lib.ptr(new_vertices), _lib.ptr(new_alpha)), fn)
+    return new_vertices, new_alpha
+
+
+def trianglemesh_loop_backward_cuda(grad_new_vertices, grad_new_alpha, vertices, alpha, topo, alpha_needs_grad):
+    """grad_new_vertices (B, V + E, 3), grad_new_alpha (B, V + E) or None, any strides; vertices, alpha and topo of the forward ->
+    grad_vertices (B, V, 3), grad_alpha (B, V) or None (``alpha_needs_grad`` False, or no alpha).  A gather with plain stores, then
+    native floating-point atomic adds of the opposite corners' 1/8 terms."""
+    fn = 'trianglemesh_loop_backward_cuda'
+    sfx, V, E = _loop_args(fn, grad_new_vertices, grad_new_alpha, topo, lambda V, E: V + E)
+    _loop_args(fn, vertices, alpha, topo, lambda V, E: V)
+    torch_check(vertices.dtype == grad_new_vertices.dtype and vertices.size(0) == grad_new_vertices.size(0),
+                f'{fn}: expected every tensor to have the same batch size and scalar type')
+    B, dev = vertices.size(0), vertices.device
+    gv = grad_new_vertices.contiguous()
+    ga = grad_new_alpha.contiguous() if grad_new_alpha is not None else None
+    v, vbs = _batch_items(vertices.detach())
+    a, abs_ = _batch_items(alpha.detach()) if alpha is not None else (None, 0)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_vertices = torch.empty((B, V, 3), dtype=v.dtype, device=dev)
+        grad_alpha = torch.empty((B, V), dtype=v.dtype, device=dev) if (a is not None and alpha_needs_grad) else None
+        if B > 0:
+            _lib.check(getattr(lib, f'kamd_trianglemesh_loop_backward_{sfx}')(
+                _lib.stream_ptr(dev), B, V, E, _lib.ptr(gv), _lib.ptr(ga), _lib.ptr(v), vbs, _lib.ptr(a), abs_,
+                *(_lib.ptr(t) for t in topo), _lib.ptr(grad_vertices), _lib.ptr(grad_alpha)), fn)
+    return grad_vertices, grad_alpha
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
+                              subdivide_trianglemesh_cuda=subdivide_trianglemesh_cuda,
+                              trianglemesh_loop_forward_cuda=trianglemesh_loop_forward_cuda,
+                              trianglemesh_loop_backward_cuda=trianglemesh_loop_backward_cuda,
                               subdivide_tetmesh_cuda=subdivide_tetmesh_cuda,
                               tetmesh_midpoints_forward_cuda=tetmesh_midpoints_forward_cuda,
                               tetmesh_midpoints_backward_cuda=tetmesh_midpoints_backward_cuda)

@@ -68,6 +68,9 @@ SIGNATURES = {
     'kamd_subdivide_tetmesh_workspace': (_sz, [_i64, _i64]),
     'kamd_subdivide_tetmesh_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
     'kamd_subdivide_tetmesh_emit': (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    'kamd_subdivide_trianglemesh_workspace': (_sz, [_i64, _i64]),
+    'kamd_subdivide_trianglemesh_edges': (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    'kamd_subdivide_trianglemesh_emit': (_i, [_vp, _i64, _i64, _vp, _vp, _i64] + [_vp] * 7),
     'kamd_tetmesh_reduce_workspace': (_sz, [_i64, _i64]),
     'kamd_cubic_meshes_workspace': (_sz, [_i64, _i, _i, _i]),
     'kamd_cubic_meshes_scan': (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
@@ -87,7 +90,9 @@ for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_marching_tetrahedra_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_tetmesh_midpoints_forward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp])
     SIGNATURES[f'kamd_tetmesh_midpoints_backward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp])
-    SIGNATURES[f'kamd_tetmesh_volume_forward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp])
+    SIGNATURES[f'kamd_trianglemesh_loop_forward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64] + [_vp] * 8)
+    SIGNATURES[f'kamd_trianglemesh_loop_backward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64] + [_vp] * 8)
+    SIGNATURES[f'kamd_tetmesh_volume_forward_{_t}'] =(_i, [_vp, _i64, _i64, _vp, _i64, _vp])
     SIGNATURES[f'kamd_tetmesh_volume_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _vp])
     SIGNATURES[f'kamd_tetmesh_equivolume_forward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i, _vp, _vp])
     SIGNATURES[f'kamd_tetmesh_equivolume_backward_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp])

@@ -1,10 +1,10 @@
 """Mesh helpers on the DIB-R path (pure torch): per-face gathers and normals, plus the vertex-set
-subdivision the voxelizer's definition rests on; and the tetrahedral-mesh operators of tetmesh.py (subdivide_tetmesh on a HIP
-edge-midpoint pipeline)."""
+subdivision the voxelizer's definition rests on; the tetrahedral-mesh operators of tetmesh.py (subdivide_tetmesh on a HIP
+edge-midpoint pipeline); and subdivide_trianglemesh of trianglemesh.py (Loop subdivision with a per-vertex alpha, on HIP)."""
 import torch
 
 __all__ = ['index_vertices_by_faces', 'face_normals', 'check_sign', 'adjacency_matrix', 'uniform_laplacian',
-           'subdivide_tetmesh', 'inverse_vertices_offset']
+           'subdivide_tetmesh', 'inverse_vertices_offset', 'subdivide_trianglemesh']
 
 
 def index_vertices_by_faces(vertices_features, faces):
@@ -173,3 +173,5 @@ def check_sign(verts, faces, points, hash_resolution=512):
 
 from . import tetmesh  # noqa: E402
 from .tetmesh import subdivide_tetmesh, inverse_vertices_offset  # noqa: E402
+from . import trianglemesh  # noqa: E402
+from .trianglemesh import subdivide_trianglemesh  # noqa: E402

@@ -1,0 +1,266 @@
+"""Generates tests/golden/subdivide_trianglemesh.npz FROM THE REFERENCE ITSELF (kaolin.ops.mesh.subdivide_trianglemesh).
+
+Run in the build container (where the reference tree is mounted):
+    python tests/golden/make_golden_subdivide_trianglemesh.py
+The reference's file is loaded by path on top of _refload's stub ``kaolin`` package; it is pure PyTorch and runs on the CPU.  The
+reference computes in float32 only and only for a batch of one (recorded below as ``err_double``, ``err_half``, ``err_batch2``):
+it is called ITEM BY ITEM with B = 1 in float32 and the results are stacked.  Per case and setting s in {default, alpha}
+(``alpha`` = the case's seeded alpha in [0, 1], ``default`` = no alpha) and iteration count k: ``<case>_<s>_<k>_vertices``
+(B, V_k, 3), every row (the old rows move).  The topology does not depend on the setting (asserted): per iteration i,
+``<case>_slots_<i>`` (F_i, 3) holds the three new ids (ab, bc, ca) of every face, from which ``child_faces`` rebuilds the
+reference's new faces exactly, iteration after iteration (asserted here; tests/subdivide_trianglemesh_golden.py holds the same
+function).  No stored row is NaN (asserted).
+
+  doc         the example of the reference's docstring (tetrahedron, valence 3, alpha 0)
+  ico         inputs and expected tensors of the reference's own TestSubdivideTrianglemesh, read from its fixtures
+              (``ico_expected_*``), next to what the reference returns for them: default alpha and zero alpha, 1 iteration
+  sphere6     geodesic_sphere(6), V = 362, F = 720 in seeded random order with rotated corners; B = 2: item 0 jittered, item 1
+              plain.  1 and 2 iterations, both settings
+  open_messy  sphere6's item 0 and topology with the faces around vertex 0 removed (a boundary), 30 duplicate faces (edges of count
+              3, and 4 between two of them), a fan on one more edge, and 10 faces with a repeated corner (self-edges).  2 iterations, both settings
+  sparse_ids  sphere6's topology mapped through the seeded injection ``sparse_ids_map`` into [0, 70 001) (id 70 000 is used);
+              B = 1, 1 iteration, both settings.  The used ids carry sphere6's item 1 and the alpha of item 0; the rows nobody
+              uses follow ``unused_rows`` below.  The reference's rows of the unused ids are NaN (asserted) and not stored
+              (stored: the rows of the 362 used ids in sphere6's vertex order, then the E edge rows)
+  grads       for sphere6 and open_messy (alpha given, 2 iterations): the reference's autograd gradients
+              ``grads_<case>_{vertices,alpha}`` under the seeded cotangent ``grads_<case>_cot`` on new_vertices, and
+              ``grads_<case>_{vertices,alpha}_tas``: per element the float64 sum of the magnitudes of the terms it accumulates
+              (asserted to bound the float64 gradient of the package's torch formulation)
+  dtypes_*    the dtypes the reference returns where it accepts the arguments
+  err_*       type and text of what the reference raises for arguments it does not accept
+"""
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+import _refload  # noqa: E402
+from kaolin_amd.ops.mesh import trianglemesh as ours  # noqa: E402
+from kaolin_amd.utils.testing import geodesic_sphere  # noqa: E402
+
+SPARSE_V = 70001
+NAME = 'subdivide_trianglemesh.npz'
+
+
+def load_modules():
+    tm = _refload.load_reference()['ops_trianglemesh']
+    sys.modules['kaolin.ops.mesh'].trianglemesh = tm
+    testing = types.ModuleType('kaolin.utils.testing')          # (the test file imports these names; the fixtures use none)
+    testing.FLOAT_TYPES, testing.check_allclose, testing.check_tensor, testing.with_seed = [('cpu', torch.float)], None, None, None
+    sys.modules['kaolin.utils.testing'] = testing
+    kat = _refload._load('ref_test_mesh_trianglemesh', 'tests/python/kaolin/ops/mesh/test_trianglemesh.py')
+    return tm, kat
+
+
+def record_error(out, name, fn):
+    try:
+        res = fn()
+    except Exception as err:  # noqa: BLE001  (the reference's own error, whatever its type)
+        out[f'err_{name}'] = np.array([type(err).__name__, str(err)])
+        return
+    out[f'dtypes_{name}'] = np.array([str(r.dtype) for r in res])
+
+
+def unused_rows(rows, channels):
+    """The values of the sparse_ids rows nobody uses: a pattern of exact eighths (tests rebuild it from this rule)."""
+    r = torch.arange(rows, dtype=torch.long).unsqueeze(1)
+    c = torch.arange(channels, dtype=torch.long).unsqueeze(0)
+    return ((r * 7 + c * 3) % 17 - 8).float() / 8
+
+
+def halves(shape, g):
+    """Seeded values from {-1, -0.5, 0, 0.5, 1}"""
+    return torch.randint(-2, 3, shape, generator=g).float() / 2
+
+
+def child_faces(faces, slots):
+    """new faces from the corners (a b c) and the new ids (ab bc ca) of every face: four consecutive rows per face.
+    (tests/subdivide_trianglemesh_golden.py holds a copy for decoding ``slots``: keep the two in step.)"""
+    a, b, c = faces.unbind(1)
+    ab, bc, ca = slots.unbind(1)
+    return torch.stack((b, bc, ab, a, ab, ca, c, ca, bc, ca, ab, bc), dim=1).reshape(-1, 3)
+
+
+def compact(ids):
+    return ids.numpy().astype(np.int16 if int(ids.max()) < 2 ** 15 else np.int32)
+
+
+def term_abs_sums(vertices, faces, alpha, cot, iterations):
+    """Per element of the gradients of vertices (B, V, 3) and alpha (B, V): the float64 sum of the magnitudes of the terms that the
+    chain of `iterations` backward passes accumulates into it.  The maps x -> new x and alpha -> new alpha are linear with
+    non-negative coefficients for alpha in [0, 1], so their magnitude sums are their own backward passes on magnitudes; the term of
+    alpha's gradient that comes from the vertex rule, sum_c g[v, c] (S[v, c] / n - x[v, c]), is bounded term by term."""
+    xs, alphas, fs = [vertices.double()], [alpha.double()], [faces]
+    for _ in range(iterations):
+        x, f, a = ours._torch_iteration(xs[-1], fs[-1], alphas[-1])
+        xs.append(x), fs.append(f), alphas.append(a)
+    gx, ga = cot.double().abs(), torch.zeros_like(alphas[-1])
+    for k in reversed(range(iterations)):
+        x, a = xs[k].clone().requires_grad_(), alphas[k].clone().requires_grad_()
+        nx, _, na = ours._torch_iteration(x, fs[k], a.detach())
+        lin_x, = torch.autograd.grad(nx, x, gx)
+        _, _, na = ours._torch_iteration(x.detach(), fs[k], a)
+        lin_a, = torch.autograd.grad(na, a, ga)
+        _, (lo, hi, proper, _, _, _, valence) = ours._torch_topology(fs[k], x.shape[1])
+        mag = torch.zeros_like(xs[k])
+        mag.index_add_(1, lo, xs[k].abs().index_select(1, hi))
+        mag.index_add_(1, hi[proper], xs[k].abs().index_select(1, lo[proper]))
+        n = valence.clamp(min=1).double()[None, :, None]
+        rule = (gx[:, :x.shape[1]] * (mag / n + xs[k].abs())).sum(-1) * (valence > 0)[None]
+        gx, ga = lin_x, lin_a + rule
+    return gx, ga
+
+
+def main():
+    tm, kat = load_modules()
+    g = torch.Generator().manual_seed(20262)
+    out = {}
+
+    def reference(vertices, faces, iterations, alpha):
+        """The reference item by item (B = 1, float32), stacked; no row NaN"""
+        assert vertices.dtype == torch.float32 and faces.dtype == torch.long
+        res = [tm.subdivide_trianglemesh(vertices[b:b + 1], faces, iterations, None if alpha is None else alpha[b:b + 1])
+               for b in range(vertices.shape[0])]
+        assert all(torch.equal(r[1], res[0][1]) for r in res)
+        return torch.cat([r[0] for r in res]), res[0][1]
+
+    def run(case, vertices, faces, alpha, iteration_counts, store=True, rows=None):
+        """Both settings at every iteration count; stores the vertices (the rows `rows` of the old vertices, then the edge rows of
+        the single iteration, when `rows` is given) and the slots of every iteration."""
+        if store:
+            out[f'{case}_vertices'], out[f'{case}_faces'], out[f'{case}_alpha'] = vertices.numpy(), compact(faces), alpha.numpy()
+        chain = [faces]
+        for k in iteration_counts:
+            topo = None
+            for setting, a in (('default', None), ('alpha', alpha)):
+                nv, nf = reference(vertices, faces, k, a)
+                assert nv.dtype == torch.float32 and nf.dtype == torch.long and nf.shape == (faces.shape[0] * 4 ** k, 3)
+                assert topo is None or torch.equal(topo, nf)
+                topo = nf
+                if rows is not None:
+                    rest = torch.ones(vertices.shape[1], dtype=torch.bool)
+                    rest[rows] = False
+                    assert k == 1 and bool(torch.isnan(nv[:, :vertices.shape[1]][:, rest]).all())    # the unused ids: NaN
+                    nv = torch.cat([nv[:, rows], nv[:, vertices.shape[1]:]], dim=1)
+                assert not bool(torch.isnan(nv).any())
+                out[f'{case}_{setting}_{k}_vertices'] = nv.numpy()
+            # the faces after k iterations, decoded from the slots of iterations 1 .. k
+            while len(chain) <= k:
+                i = len(chain)
+                mid = reference(vertices, faces, i, None)[1] if i < k else topo
+                F = chain[-1].shape[0]
+                slots = torch.stack([mid[1::4, 1], mid[0::4, 1], mid[1::4, 2]], dim=1)               # ab, bc, ca
+                assert slots.shape == (F, 3) and torch.equal(child_faces(chain[-1], slots), mid)
+                out[f'{case}_slots_{i}'] = compact(slots)
+                chain.append(mid)
+        return chain
+
+    # ---- doc ---------------------------------------------------------------------------------------------------------------
+    run('doc', torch.tensor([[[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]]], dtype=torch.float),
+        torch.tensor([[0, 1, 2], [0, 1, 3], [0, 2, 3], [1, 2, 3]]), torch.zeros(1, 4), (1,))
+
+    # ---- ico: the reference's own test, its fixtures read as data ----------------------------------------------------------
+    t = kat.TestSubdivideTrianglemesh()
+    fx = {n: getattr(kat.TestSubdivideTrianglemesh, n).__wrapped__(t, 'cpu') for n in
+          ('vertices_icosahedron', 'faces_icosahedron', 'expected_vertices_default_alpha', 'expected_vertices_zero_alpha',
+           'expected_faces_icosahedron_1_iter')}
+    run('ico', fx['vertices_icosahedron'], fx['faces_icosahedron'], torch.zeros(1, 12), (1,))
+    out['ico_expected_default_vertices'] = fx['expected_vertices_default_alpha'].numpy()
+    out['ico_expected_zero_vertices'] = fx['expected_vertices_zero_alpha'].numpy()
+    out['ico_expected_faces'] = compact(fx['expected_faces_icosahedron_1_iter'])
+    assert torch.allclose(torch.from_numpy(out['ico_default_1_vertices']), fx['expected_vertices_default_alpha'], atol=1e-4)
+    assert torch.allclose(torch.from_numpy(out['ico_alpha_1_vertices']), fx['expected_vertices_zero_alpha'], atol=1e-4)
+
+    # ---- sphere6 -----------------------------------------------------------------------------------------------------------
+    sv, sf = geodesic_sphere(6)
+    assert sv.shape == (362, 3) and sf.shape == (720, 3)
+    sf = sf[torch.randperm(720, generator=g)]
+    turn = torch.randint(0, 3, (720,), generator=g)
+    sf = torch.stack([sf[torch.arange(720), (turn + k) % 3] for k in range(3)], dim=1)
+    sv = sv.float()
+    sv = torch.stack([sv + (torch.rand(sv.shape, generator=g) - 0.5) * 0.02, sv])
+    sa = torch.rand(2, 362, generator=g)
+    chain = run('sphere6', sv, sf, sa, (1, 2))
+    assert chain[1].shape[0] == 2880 and int(chain[1].max()) == 362 + 1080 - 1 and int(chain[2].max()) == 1442 + 4320 - 1
+
+    # ---- open_messy --------------------------------------------------------------------------------------------------------
+    keep = ~(sf == 0).any(dim=1)
+    assert int((~keep).sum()) in (5, 6)
+    mf = sf[keep]
+    quad = mf[100]                                                                          # an edge of count 3: a fan on (a, b)
+    far = next(v for v in range(1, 362) if v not in quad.tolist() and not ((mf == quad[0]).any(1) & (mf == v).any(1)).any())
+    # ten faces with a repeated corner: (a, a, a) and (a, b, a) in turn; the first one gives vertex 0 a self-edge, its only edge
+    deg = torch.tensor([[a, a, a] if i % 2 == 0 else [a, 10 + i, a] for i, a in enumerate([0] + list(range(301, 310)))])
+    mf = torch.cat([mf, mf[:30], torch.stack((quad[0], quad[1], torch.tensor(far)))[None], deg])
+    out['open_messy_faces'] = compact(mf)
+    mv, ma = sv[:1], sa[:1]
+    run('open_messy', mv, mf, ma, (2,), store=False)
+    _, (_, _, proper, slot_edge, _, _, valence) = ours._torch_topology(mf, 362)
+    counts = torch.bincount(slot_edge)
+    assert int((counts == 1).sum()) > 0 and int((counts == 3).sum()) > 0 and int((counts == 4).sum()) > 0 and int((counts >= 3).sum()) >= 60
+    assert int((~proper).sum()) == 10 and int(valence.min()) > 0
+
+    # ---- sparse_ids --------------------------------------------------------------------------------------------------------
+    id_map = torch.sort(torch.randperm(SPARSE_V - 1, generator=g)[:361]).values
+    id_map = torch.cat([id_map, torch.tensor([SPARSE_V - 1])])[torch.randperm(362, generator=g)]
+    assert id_map.unique().numel() == 362 and int(id_map.max()) == SPARSE_V - 1 and int(id_map.min()) >= 0
+    out['sparse_ids_map'] = id_map.numpy().astype(np.int32)
+    pf = id_map[sf]
+    pv, pa = unused_rows(SPARSE_V, 3)[None].clone(), unused_rows(SPARSE_V, 1)[None, :, 0].abs().clone()
+    pv[0, id_map], pa[0, id_map] = sv[1], sa[0]
+    run('sparse_ids', pv, pf, pa, (1,), store=False, rows=id_map)
+
+    # ---- grads -------------------------------------------------------------------------------------------------------------
+    for case, (vertices, faces, alpha) in {'sphere6': (sv, sf, sa), 'open_messy': (mv, mf, ma)}.items():
+        B, V = vertices.shape[:2]
+        rows = out[f'{case}_alpha_2_vertices'].shape[1]
+        cot = halves((B, rows, 3), g)
+        out[f'grads_{case}_cot'] = cot.numpy()
+        gv, gal = [], []
+        for b in range(B):
+            p, a = vertices[b:b + 1].clone().requires_grad_(), alpha[b:b + 1].clone().requires_grad_()
+            nv, _ = tm.subdivide_trianglemesh(p, faces, 2, a)
+            (nv * cot[b:b + 1]).sum().backward()
+            gv.append(p.grad), gal.append(a.grad)
+        out[f'grads_{case}_vertices'], out[f'grads_{case}_alpha'] = torch.cat(gv).numpy(), torch.cat(gal).numpy()
+        assert not np.isnan(out[f'grads_{case}_vertices']).any() and not np.isnan(out[f'grads_{case}_alpha']).any()
+        p, a = vertices.double().requires_grad_(), alpha.double().requires_grad_()
+        nv, _ = ours.subdivide_trianglemesh(p, faces, 2, a)
+        (nv * cot.double()).sum().backward()
+        tv, ta = term_abs_sums(vertices, faces, alpha, cot, 2)
+        assert bool((tv + 1e-300 >= p.grad.abs() * (1 - 1e-9)).all()) and bool((ta + 1e-300 >= a.grad.abs() * (1 - 1e-9)).all())
+        out[f'grads_{case}_vertices_tas'], out[f'grads_{case}_alpha_tas'] = tv.numpy(), ta.numpy()
+
+    # ---- dtypes and errors -------------------------------------------------------------------------------------------------
+    ev, ef, ea = out['doc_vertices'], torch.from_numpy(out['doc_faces']).long(), torch.zeros(1, 4)
+    ev = torch.from_numpy(ev)
+    record_error(out, 'double', lambda: tm.subdivide_trianglemesh(ev.double(), ef, 1, ea.double()))
+    record_error(out, 'half', lambda: tm.subdivide_trianglemesh(ev.half(), ef, 1, ea.half()))
+    record_error(out, 'batch2', lambda: tm.subdivide_trianglemesh(ev.expand(2, -1, -1), ef, 1, ea.expand(2, -1)))
+    record_error(out, 'int32_faces', lambda: tm.subdivide_trianglemesh(ev, ef.int(), 1, ea))
+    record_error(out, 'alpha3', lambda: tm.subdivide_trianglemesh(ev, ef, 1, ea.unsqueeze(-1)))
+    record_error(out, 'faces_float', lambda: tm.subdivide_trianglemesh(ev, ef.float(), 1, ea))
+    record_error(out, 'faces_1d', lambda: tm.subdivide_trianglemesh(ev, ef.reshape(-1), 1, ea))
+    record_error(out, 'vertices_2d', lambda: tm.subdivide_trianglemesh(ev[0], ef, 1, ea))
+    record_error(out, 'alpha_rows', lambda: tm.subdivide_trianglemesh(ev, ef, 1, ea[:, :3]))
+    record_error(out, 'iterations_float', lambda: tm.subdivide_trianglemesh(ev, ef, 1.0, ea))
+
+    path = os.path.join(HERE, NAME)
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    largest = max(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if f != NAME)
+    assert size < largest, (size, largest)
+    print('wrote', NAME, len(out), 'arrays', size, 'bytes')
+    for k in sorted(out):
+        if k.startswith('err_') or k.startswith('dtypes_'):
+            print(k, list(out[k]))
+
+
+if __name__ == '__main__':
+    main()
