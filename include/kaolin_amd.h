@@ -965,6 +965,77 @@ int kamd_tetmesh_amips_backward_f64(void* stream, int64_t B, int64_t T, const do
                                     double* grad_tet_vertices, double* grad_inverse_offset_matrix);
 
 /* ------------------------------------------------------------------------- */
+/* ops.spc: the core of the structured point cloud (SPC) operators (reference: */
+/* kaolin/csrc/ops/spc/{spc,query,feature_grids,point_utils}*; csrc/spc.hip).  */
+/* Morton layout: bit 3i = z_i, 3i+1 = y_i, 3i+2 = x_i, 15 bits a coordinate.  */
+/* points are int16 (N,3), codes int64, octrees uint8, exsum int32 in the      */
+/* current layout (per octree the inclusive sum of the bit counts, num_bytes   */
+/* entries).  Every kernel receives the sizes of the buffers it indexes and    */
+/* compares each data-derived index with them: an index out of range is a miss */
+/* (query) or a skipped write (the others), never an access.                   */
+/*   points_to_morton / morton_to_points / points_to_corners: one launch each. */
+/*   octree_build: codes (any order, duplicates allowed unless `sorted`) are   */
+/*     masked to 3*level bits, sorted (keys-only radix sort, 8 bits a pass),   */
+/*     made unique, and every level is built bottom-up in the workspace        */
+/*     (kamd_spc_octree_workspace(n, level) bytes).  host_sizes (HOST memory,  */
+/*     1 + level int64: unique codes, then nodes per level root first) is the  */
+/*     one host read: the call synchronises the stream.  octree_gather then    */
+/*     writes the octree_bytes = sum of the level sizes bytes.  1 <= level <=  */
+/*     15, n >= 1.                                                             */
+/*   scan_octrees: octrees (total_bytes) of B items, starts (DEVICE, B + 1      */
+/*     int64, starts[0] = 0, starts[B] = total_bytes, items non-empty);        */
+/*     total_bytes * 8 < 2^31.  Writes exsum (total_bytes) and reads back, once */
+/*     for the batch, host_pyramids (HOST memory, B x 35 int32: the (2, 17)    */
+/*     pyramid of the item, then its depth).  The walk of an item clamps its   */
+/*     index to the item's length.  workspace: kamd_spc_scan_workspace bytes.  */
+/*   generate_points: meta (DEVICE, B x (2 + 2 (max_level + 2)) int64: the     */
+/*     item's first octree byte, its first point, pyramid[0][:], pyramid[1][:]).*/
+/*     max_level launches (grid.y = item), no host read.  num_bytes and         */
+/*     num_points bound every index.  B <= 65535.                              */
+/*   query / query_multiscale: coords (Q,3) half / float / double in [-1,1],   */
+/*     read in place; result int64 (Q) / (Q, level + 1); -1 = miss.  One       */
+/*     launch, no host read, no allocation: capturable.  level <= 15.          */
+/*   to_dense: points = the packed point hierarchy (num_points rows), meta     */
+/*     (DEVICE, 2 B + 1 int64: the B + 1 prefix of the items' rows at the       */
+/*     level, then every item's first point of the level); features (rows, C), */
+/*     grid (B, C, E, E, E), E = 2^level.  forward = zero fill + one thread     */
+/*     per (row, channel); backward = the matching gather.  No atomics.        */
+/* ------------------------------------------------------------------------- */
+int kamd_spc_points_to_morton(void* stream, int64_t n, const int16_t* points, int64_t* morton);
+int kamd_spc_morton_to_points(void* stream, int64_t n, const int64_t* morton, int16_t* points);
+int kamd_spc_points_to_corners(void* stream, int64_t n, const int16_t* points, int16_t* corners);
+size_t kamd_spc_octree_workspace(int64_t n, int level);
+int kamd_spc_octree_build(void* stream, int64_t n, int level, const int64_t* morton, int sorted, void* workspace,
+                          size_t workspace_bytes, int64_t* host_sizes);
+int kamd_spc_octree_gather(void* stream, int64_t n, int level, const void* workspace, int64_t octree_bytes, uint8_t* octree);
+size_t kamd_spc_scan_workspace(int64_t total_bytes, int64_t B);
+int kamd_spc_scan_octrees(void* stream, int64_t total_bytes, int64_t B, const uint8_t* octrees, const int64_t* starts,
+                          int32_t* exsum, void* workspace, int32_t* host_pyramids);
+int kamd_spc_generate_points(void* stream, int64_t B, int max_level, int64_t num_bytes, int64_t num_points,
+                             const uint8_t* octrees, const int32_t* exsum, const int64_t* meta, int64_t max_level_nodes,
+                             int16_t* points);
+int kamd_spc_query_f16(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree, const int32_t* exsum,
+                       const void* coords, int64_t* pidx);
+int kamd_spc_query_f32(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree, const int32_t* exsum,
+                       const float* coords, int64_t* pidx);
+int kamd_spc_query_f64(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree, const int32_t* exsum,
+                       const double* coords, int64_t* pidx);
+int kamd_spc_query_multiscale_f16(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree,
+                                  const int32_t* exsum, const void* coords, int64_t* pidx);
+int kamd_spc_query_multiscale_f32(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree,
+                                  const int32_t* exsum, const float* coords, int64_t* pidx);
+int kamd_spc_query_multiscale_f64(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree,
+                                  const int32_t* exsum, const double* coords, int64_t* pidx);
+int kamd_spc_to_dense_forward_f32(void* stream, int64_t B, int64_t C, int level, int64_t rows, int64_t num_points,
+                                  const int16_t* points, const int64_t* meta, const float* features, float* grid);
+int kamd_spc_to_dense_forward_f64(void* stream, int64_t B, int64_t C, int level, int64_t rows, int64_t num_points,
+                                  const int16_t* points, const int64_t* meta, const double* features, double* grid);
+int kamd_spc_to_dense_backward_f32(void* stream, int64_t B, int64_t C, int level, int64_t rows, int64_t num_points,
+                                   const int16_t* points, const int64_t* meta, const float* grad_grid, float* grad_features);
+int kamd_spc_to_dense_backward_f64(void* stream, int64_t B, int64_t C, int level, int64_t rows, int64_t num_points,
+                                   const int16_t* points, const int64_t* meta, const double* grad_grid, double* grad_features);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -572,6 +572,257 @@ def trianglemesh_loop_backward_cuda(grad_new_vertices, grad_new_alpha, vertices,
     return grad_vertices, grad_alpha
 
 
+# ---- kaolin._C.ops.spc: the SPC core on csrc/spc.hip ---------------------------------------------------------------------
+SPC_MAX_LEVEL = 15      # KAOLIN_SPC_MAX_LEVELS
+
+
+def _spc_points_arg(fn, points):
+    torch_check(points.is_cuda, f'{fn}: points must be a CUDA tensor')
+    torch_check(points.dtype == torch.int16, f'{fn}: points must be short')
+    torch_check(points.dim() == 2 and points.size(1) == 3, f'{fn}: points must be Nx3')
+    torch_check(points.is_contiguous(), f'{fn}: points must be contiguous')
+
+
+def points_to_morton_cuda(points):
+    """reference: point_utils.cpp ``points_to_morton_cuda``: points (N, 3) int16 -> Morton codes (N) int64 (bit 3i = z, 3i + 1 = y,
+    3i + 2 = x, the low 15 bits of every coordinate).  One launch, capturable."""
+    fn = 'points_to_morton_cuda'
+    _spc_points_arg(fn, points)
+    lib = _lib.load()
+    with _lib.on_device(points.device):
+        morton = torch.empty(points.size(0), dtype=torch.long, device=points.device)
+        _lib.check(lib.kamd_spc_points_to_morton(_lib.stream_ptr(points.device), points.size(0), _lib.ptr(points), _lib.ptr(morton)), fn)
+    return morton
+
+
+def morton_to_points_cuda(morton):
+    """reference: point_utils.cpp ``morton_to_points_cuda``: codes (N) int64 -> points (N, 3) int16.  One launch, capturable."""
+    fn = 'morton_to_points_cuda'
+    torch_check(morton.is_cuda, f'{fn}: morton must be a CUDA tensor')
+    torch_check(morton.dtype == torch.long and morton.dim() == 1, f'{fn}: morton must be long, of size {{num_points}}')
+    torch_check(morton.is_contiguous(), f'{fn}: morton must be contiguous')
+    lib = _lib.load()
+    with _lib.on_device(morton.device):
+        points = torch.empty((morton.size(0), 3), dtype=torch.int16, device=morton.device)
+        _lib.check(lib.kamd_spc_morton_to_points(_lib.stream_ptr(morton.device), morton.size(0), _lib.ptr(morton), _lib.ptr(points)), fn)
+    return points
+
+
+def points_to_corners_cuda(points):
+    """reference: point_utils.cpp ``points_to_corners_cuda``: points (N, 3) int16 -> (N, 8, 3) int16, corner j = point +
+    (j >> 2, (j >> 1) & 1, j & 1).  One launch, capturable."""
+    fn = 'points_to_corners_cuda'
+    _spc_points_arg(fn, points)
+    lib = _lib.load()
+    with _lib.on_device(points.device):
+        corners = torch.empty((points.size(0), 8, 3), dtype=torch.int16, device=points.device)
+        _lib.check(lib.kamd_spc_points_to_corners(_lib.stream_ptr(points.device), points.size(0), _lib.ptr(points), _lib.ptr(corners)), fn)
+    return corners
+
+
+def morton_to_octree(mortons, level, sorted=True):
+    """reference: spc.cpp ``morton_to_octree``: Morton codes (N) int64 of points of ``level`` -> octree (num_bytes) uint8, levels root
+    first.  ``sorted=True`` is the reference's contract (unique codes in ascending order); ``sorted=False`` (ours) takes any order and
+    duplicates: the codes go through the keys-only radix sort over their 3 * level significant bits.  Bits above those are
+    dropped.  The host reads the level sizes once (the reference: once per level): the call synchronises the current stream and
+    cannot be captured in a graph."""
+    fn = 'morton_to_octree'
+    torch_check(mortons.is_cuda, f'{fn}: mortons must be a CUDA tensor')
+    torch_check(mortons.dtype == torch.long and mortons.dim() == 1, f'{fn}: mortons must be long, of size {{num_points}}')
+    torch_check(mortons.is_contiguous(), f'{fn}: mortons must be contiguous')
+    level, n, dev = int(level), mortons.size(0), mortons.device
+    torch_check(0 <= level <= SPC_MAX_LEVEL, f'{fn}: level must be in [0, {SPC_MAX_LEVEL}]')
+    torch_check(n > 0, f'{fn}: no points')
+    if level == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_spc_octree_workspace(n, level)
+        ws = _lib.workspace(nbytes, dev)
+        sizes = (ctypes.c_int64 * (1 + level))()
+        _lib.check(lib.kamd_spc_octree_build(sp, n, level, _lib.ptr(mortons), int(bool(sorted)), _lib.ptr(ws), nbytes,
+                                             ctypes.cast(sizes, ctypes.c_void_p)), fn)
+        octree_bytes = sum(sizes[1:])                          # data-dependent size: the one host read
+        octree = torch.empty(octree_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.kamd_spc_octree_gather(sp, n, level, _lib.ptr(ws), octree_bytes, _lib.ptr(octree)), fn)
+    return octree
+
+
+def points_to_octree(points, level, sorted=True):
+    """reference: spc.cpp ``points_to_octree``: points (N, 3) int16 of ``level`` -> octree; see morton_to_octree."""
+    _spc_points_arg('points_to_octree', points)
+    torch_check(points.size(0) > 0, 'points_to_octree: no points')
+    return morton_to_octree(points_to_morton_cuda(points), level, sorted=sorted)
+
+
+def scan_octrees_cuda(octrees, lengths):
+    """reference: spc.cpp:79-107 ``scan_octrees_cuda``: octrees (num_bytes) uint8 CUDA, lengths (B) int32 CPU -> (max_level,
+    pyramids (B, 2, max_level + 2) int32 CPU, exsum (num_bytes) int32 CUDA: per octree the inclusive sum of the bit counts).
+    Four launches and ONE host read for the batch (the reference: one read per level and item).  ValueError when the items differ
+    in depth or an item does not account for its bytes exactly."""
+    fn = 'scan_octrees_cuda'
+    torch_check(octrees.is_cuda, f'{fn}: octrees must be a CUDA tensor')
+    torch_check(octrees.dtype == torch.uint8 and octrees.dim() == 1, f'{fn}: octrees must be a 1D byte tensor')
+    torch_check(octrees.is_contiguous(), f'{fn}: octrees must be contiguous')
+    torch_check(not lengths.is_cuda and lengths.dim() == 1, f'{fn}: lengths must be a 1D CPU tensor')
+    lens = [int(v) for v in lengths.tolist()]
+    B, total, dev = len(lens), sum(lens), octrees.device
+    if B == 0 or min(lens) < 1:
+        raise ValueError(f'{fn}: every octree needs at least one byte, got lengths {lens}')
+    if total != octrees.numel():
+        raise ValueError(f'{fn}: lengths sum to {total}, octrees holds {octrees.numel()} bytes')
+    if total * 8 >= 2 ** 31:
+        raise ValueError(f'{fn}: {total} bytes: sum(lengths) * 8 must stay below 2^31')
+    lib = _lib.load()
+    host = (ctypes.c_int32 * (35 * B))()
+    with _lib.on_device(dev):
+        starts = torch.tensor([0] + lens, dtype=torch.long).cumsum(0).to(dev)
+        exsum = torch.empty(total, dtype=torch.int32, device=dev)
+        ws = _lib.workspace(lib.kamd_spc_scan_workspace(total, B), dev)
+        _lib.check(lib.kamd_spc_scan_octrees(_lib.stream_ptr(dev), total, B, _lib.ptr(octrees), _lib.ptr(starts), _lib.ptr(exsum),
+                                             _lib.ptr(ws), ctypes.cast(host, ctypes.c_void_p)), fn)
+    full = torch.tensor(list(host), dtype=torch.int32).reshape(B, 35)      # the one host read, for the whole batch
+    return finish_scan(fn, full[:, :34].reshape(B, 2, 17), full[:, 34].tolist(), lens) + (exsum,)
+
+
+def finish_scan(fn, full_pyramids, depths, lens):
+    """The checks scan_octrees makes after its read-back: one depth for the batch, every byte accounted for."""
+    max_level = depths[0]
+    if any(d != max_level for d in depths):
+        raise ValueError(f'{fn}: all octrees of a batch must have the same depth, got {depths}')
+    used = full_pyramids[:, 0, :max_level].sum(1).tolist()
+    if used != lens:
+        raise ValueError(f'{fn}: the levels of the octrees account for {used} bytes, lengths says {lens} '
+                         '(an octree is truncated, padded or deeper than 15 levels)')
+    return max_level, full_pyramids[:, :, :max_level + 2].contiguous()
+
+
+def _spc_exsum_arg(fn, exsum, num_bytes):
+    torch_check(exsum.is_cuda and exsum.dtype == torch.int32 and exsum.dim() == 1, f'{fn}: exsum must be a 1D CUDA int tensor')
+    torch_check(exsum.is_contiguous(), f'{fn}: exsum must be contiguous')
+    if exsum.numel() != num_bytes:
+        raise ValueError(f'{fn}: exsum has {exsum.numel()} entries for {num_bytes} octree bytes; only the current layout '
+                         '(num_bytes entries, inclusive sums) is accepted, not the legacy one with a leading 0 per octree')
+
+
+def spc_generate_meta(pyramids):
+    """(meta rows (B, 2 + 2 (max_level + 2)) int64 CPU, num_bytes, num_points, largest level) of a CPU pyramid"""
+    p = pyramids.to(torch.long)
+    L = p.size(2) - 2
+    nbytes, npoints = p[:, 1, L], p[:, 1, L + 1]
+    ostart = torch.cumsum(nbytes, 0) - nbytes
+    pstart = torch.cumsum(npoints, 0) - npoints
+    meta = torch.cat([ostart[:, None], pstart[:, None], p[:, 0, :], p[:, 1, :]], dim=1).contiguous()
+    return meta, int(nbytes.sum()), int(npoints.sum()), int(p[:, 0, :].max()) if p.numel() else 0
+
+
+def generate_points_cuda(octrees, pyramid, exsum):
+    """reference: spc.cpp:109-134 ``generate_points_cuda``: octrees (num_bytes) uint8, pyramid (B, 2, max_level + 2) int32 CPU, exsum
+    (num_bytes) int32 -> point hierarchies (num_points, 3) int16.  max_level launches for the whole batch, no host read (the
+    reference: a launch per level and item, and a host write per item)."""
+    fn = 'generate_points_cuda'
+    torch_check(octrees.is_cuda, f'{fn}: octrees must be a CUDA tensor')
+    torch_check(octrees.dtype == torch.uint8 and octrees.dim() == 1 and octrees.is_contiguous(), f'{fn}: octrees must be a contiguous 1D byte tensor')
+    torch_check(not pyramid.is_cuda and pyramid.dim() == 3 and pyramid.size(1) == 2, f'{fn}: pyramid must be a CPU tensor of size {{batch_size, 2, max_level + 2}}')
+    _spc_exsum_arg(fn, exsum, octrees.numel())
+    B, L, dev = pyramid.size(0), pyramid.size(2) - 2, octrees.device
+    torch_check(0 <= L <= SPC_MAX_LEVEL, f'{fn}: max_level must be in [0, {SPC_MAX_LEVEL}]')
+    torch_check(B <= 65535, f'{fn}: more than 65535 octrees in a batch')
+    meta, nbytes, npoints, widest = spc_generate_meta(pyramid)
+    if nbytes != octrees.numel():
+        raise ValueError(f'{fn}: the pyramids describe {nbytes} octree bytes, octrees holds {octrees.numel()}')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        points = torch.zeros((npoints, 3), dtype=torch.int16, device=dev) if L == 0 else \
+            torch.empty((npoints, 3), dtype=torch.int16, device=dev)
+        if npoints > 0 and L > 0:
+            meta = meta.to(dev)
+            _lib.check(lib.kamd_spc_generate_points(_lib.stream_ptr(dev), B, L, nbytes, npoints, _lib.ptr(octrees), _lib.ptr(exsum),
+                                                    _lib.ptr(meta), widest, _lib.ptr(points)), fn)
+    return points
+
+
+def _spc_query(fn, multiscale, octree, exsum, query_coords, level):
+    torch_check(octree.is_cuda and exsum.is_cuda and query_coords.is_cuda, f'{fn}: octree, prefix_sum and query_coords must be CUDA tensors')
+    torch_check(octree.device == exsum.device == query_coords.device, f'{fn}: expected every tensor on the same device')
+    torch_check(octree.dtype == torch.uint8 and octree.dim() == 1, f'{fn}: octree must be a 1D byte tensor')
+    torch_check(octree.is_contiguous() and query_coords.is_contiguous(), f'{fn}: expected contiguous tensors')
+    torch_check(query_coords.dim() == 2 and query_coords.size(1) == 3, f'{fn}: query_coords must be Nx3')
+    _spc_exsum_arg(fn, exsum, octree.numel())
+    sfx = _lib.dtype_suffix(query_coords.dtype, fn, allowed=('f16', 'f32', 'f64'))
+    level = int(level)
+    torch_check(0 <= level <= SPC_MAX_LEVEL, f'{fn}: level must be in [0, {SPC_MAX_LEVEL}]')
+    Q, dev = query_coords.size(0), octree.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        if octree.numel() == 0:
+            return torch.full((Q, level + 1) if multiscale else (Q,), -1, dtype=torch.long, device=dev)
+        pidx = torch.empty((Q, level + 1) if multiscale else (Q,), dtype=torch.long, device=dev)
+        _lib.check(getattr(lib, f'kamd_spc_query_{"multiscale_" if multiscale else ""}{sfx}')(
+            _lib.stream_ptr(dev), Q, level, octree.numel(), _lib.ptr(octree), _lib.ptr(exsum), _lib.ptr(query_coords), _lib.ptr(pidx)), fn)
+    return pidx
+
+
+def query_cuda(octree, prefix_sum, query_coords, target_level):
+    """reference: query.cpp:49-73 ``query_cuda``: octree (num_bytes) uint8, prefix_sum (num_bytes) int32, query_coords (Q, 3) half /
+    float / double in [-1, 1], read in place -> point index (Q), -1 for a miss; int64 here (the reference returns int32 and its
+    Python layer converts).  One launch, no host read: capturable."""
+    return _spc_query('query_cuda', False, octree, prefix_sum, query_coords, target_level)
+
+
+def query_multiscale_cuda(octree, prefix_sum, query_coords, target_level):
+    """reference: query.cpp:75-99 ``query_multiscale_cuda``: as query_cuda -> (Q, target_level + 1): the index of the point and of
+    every ancestor, -1 from the first level that misses."""
+    return _spc_query('query_multiscale_cuda', True, octree, prefix_sum, query_coords, target_level)
+
+
+def _spc_to_dense(fn, backward, points, level, pyramid, features, grad_outputs=None):
+    torch_check(points.is_cuda and features.is_cuda, f'{fn}: points and features must be CUDA tensors')
+    torch_check(not pyramid.is_cuda and pyramid.dim() == 3 and pyramid.size(1) == 2, f'{fn}: pyramid must be a CPU tensor of size {{batch_size, 2, max_level + 2}}')
+    torch_check(points.dtype == torch.int16 and points.dim() == 2 and points.size(1) == 3 and points.is_contiguous(),
+                f'{fn}: points must be a contiguous short tensor of size {{num_points, 3}}')
+    torch_check(features.dim() == 2 and features.is_contiguous(), f'{fn}: features must be a contiguous tensor of size {{num_inputs, feature_dim}}')
+    sfx = _lib.dtype_suffix(features.dtype, fn)
+    level = int(level)
+    B, L = pyramid.size(0), pyramid.size(2) - 2
+    torch_check(0 <= level <= L <= SPC_MAX_LEVEL, f'{fn}: level must be in [0, max_level], max_level at most {SPC_MAX_LEVEL}')
+    p = pyramid.to(torch.long)
+    counts = p[:, 0, level]
+    rows, C, E, dev = int(counts.sum()), features.size(1), 1 << level, features.device
+    torch_check(features.size(0) == rows, f'{fn}: features has {features.size(0)} rows, level {level} of the batch has {rows} points')
+    npoints = p[:, 1, L + 1]
+    first = torch.cumsum(npoints, 0) - npoints + p[:, 1, level]
+    meta = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(counts, 0), first])
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        if backward:
+            torch_check(grad_outputs.is_cuda and grad_outputs.is_contiguous() and grad_outputs.dtype == features.dtype and
+                        tuple(grad_outputs.shape) == (B, C, E, E, E), f'{fn}: grad_outputs must be a contiguous CUDA tensor of size {(B, C, E, E, E)}')
+            out = torch.empty_like(features)
+            src = grad_outputs
+        else:
+            out = torch.empty((B, C, E, E, E), dtype=features.dtype, device=dev)
+            src = features
+        if out.numel() > 0:
+            meta = meta.to(dev)
+            _lib.check(getattr(lib, f'kamd_spc_to_dense_{"backward" if backward else "forward"}_{sfx}')(
+                _lib.stream_ptr(dev), B, C, level, rows, points.size(0), _lib.ptr(points), _lib.ptr(meta), _lib.ptr(src), _lib.ptr(out)), fn)
+    return out
+
+
+def to_dense_forward(points, level, pyramid, features):
+    """reference: feature_grids.cpp:47-78 ``to_dense_forward``: points = packed point hierarchies (num_points, 3) int16, pyramid CPU,
+    features (rows at ``level``, C) float32 / float64 -> (B, C, 2^level, 2^level, 2^level): a zero fill and one thread per (point,
+    channel), the whole batch in one launch (the reference: one launch per item, float only)."""
+    return _spc_to_dense('to_dense_forward', False, points, level, pyramid, features)
+
+
+def to_dense_backward(points, level, pyramid, features, grad_outputs):
+    """reference: feature_grids.cpp:81-106 ``to_dense_backward``: the matching gather -> grad_features, of the size of features."""
+    return _spc_to_dense('to_dense_backward', True, points, level, pyramid, features, grad_outputs)
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
@@ -584,3 +835,9 @@ mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_in
 conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
                                      marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda,
                                      voxelgrids_to_cubic_meshes_cuda=voxelgrids_to_cubic_meshes_cuda)
+spc = _types.SimpleNamespace(points_to_morton_cuda=points_to_morton_cuda, morton_to_points_cuda=morton_to_points_cuda,
+                             points_to_corners_cuda=points_to_corners_cuda, points_to_octree=points_to_octree,
+                             morton_to_octree=morton_to_octree, scan_octrees_cuda=scan_octrees_cuda,
+                             generate_points_cuda=generate_points_cuda, query_cuda=query_cuda,
+                             query_multiscale_cuda=query_multiscale_cuda, to_dense_forward=to_dense_forward,
+                             to_dense_backward=to_dense_backward)

@@ -8,6 +8,7 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
                                 voxelgrids_to_cubic_meshes (sort-free HIP pipeline)
     kaolin_amd.ops.mesh         subdivide_tetmesh (HIP edge-midpoint pipeline), inverse_vertices_offset, check_sign,
                                 subdivide_trianglemesh (Loop subdivision with a per-vertex alpha, HIP pipeline)
+    kaolin_amd.ops.spc          the SPC core: scan_octrees, generate_points, unbatched_query, to_dense, unbatched_points_to_octree (HIP)
     kaolin_amd.ops.voxelgrid    fill (HIP flood fill over bit grids), downsample, extract_surface, extract_odms, project_odms
     kaolin_amd.metrics.voxelgrid  iou
     kaolin_amd.metrics.tetmesh  tetrahedron_volume, equivolume, amips (fused HIP kernels, atomic-free reductions)

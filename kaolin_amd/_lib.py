@@ -76,7 +76,22 @@ SIGNATURES = {
     'kamd_cubic_meshes_scan': (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
     'kamd_cubic_meshes_emit_vertices': (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
     'kamd_cubic_meshes_emit_faces': (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _vp]),
+    'kamd_spc_points_to_morton': (_i, [_vp, _i64, _vp, _vp]),
+    'kamd_spc_morton_to_points': (_i, [_vp, _i64, _vp, _vp]),
+    'kamd_spc_points_to_corners': (_i, [_vp, _i64, _vp, _vp]),
+    'kamd_spc_octree_workspace': (_sz, [_i64, _i]),
+    'kamd_spc_octree_build': (_i, [_vp, _i64, _i, _vp, _i, _vp, _sz, _vp]),
+    'kamd_spc_octree_gather': (_i, [_vp, _i64, _i, _vp, _i64, _vp]),
+    'kamd_spc_scan_workspace': (_sz, [_i64, _i64]),
+    'kamd_spc_scan_octrees': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'kamd_spc_generate_points': (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
+for _t in ('f16', 'f32', 'f64'):
+    SIGNATURES[f'kamd_spc_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_spc_query_multiscale_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp])
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_spc_to_dense_forward_{_t}'] = (_i, [_vp, _i64, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_spc_to_dense_backward_{_t}'] = (_i, [_vp, _i64, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64', 'f16', 'u8', 'i16', 'i32', 'i64'):
     SIGNATURES[f'kamd_sided_distance_forward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_sided_distance_backward_{_t}'] = (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp])

@@ -277,3 +277,17 @@ def kuhn_grid(n, dtype=torch.float):
         v2 = v1 + step[order[1]]
         tets.append(torch.stack([base, v1, v2, v2 + step[order[2]]], dim=-1))
     return vertices, torch.stack(tets, dim=1).reshape(-1, 4)
+
+
+def random_spc_octrees(batch_size, max_level, device='cpu'):
+    """A batch of random SPC octrees, every one of depth exactly `max_level`: per item a random number (1 to 8^max_level, at most
+    2 000) of random cells of the 2^max_level grid, through the torch octree build on the CPU (so the batch is the same on every
+    device).  Returns (octrees (num_bytes) uint8 on `device`, lengths (batch_size) int32 CPU)."""
+    from ..ops.spc import unbatched_points_to_octree
+    octrees = []
+    for _ in range(batch_size):
+        n = int(torch.randint(1, min(8 ** max_level, 2000) + 1, (1,)))
+        points = torch.randint(0, 2 ** max_level, (n, 3), dtype=torch.int16)
+        octrees.append(unbatched_points_to_octree(points, max_level))
+    lengths = torch.tensor([o.numel() for o in octrees], dtype=torch.int32)
+    return torch.cat(octrees).to(device), lengths
