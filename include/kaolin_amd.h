@@ -1036,6 +1036,53 @@ int kamd_spc_to_dense_backward_f64(void* stream, int64_t B, int64_t C, int level
                                    const int16_t* points, const int64_t* meta, const double* grad_grid, double* grad_features);
 
 /* ------------------------------------------------------------------------- */
+/* render.spc: octree ray tracing and the packed ray operators (reference:     */
+/* kaolin/csrc/render/spc; csrc/spc_raytrace.hip).                             */
+/*   raytrace: N rays (origin, direction (N,3) float32) through ONE octree     */
+/*     (num_bytes bytes, exsum in the current layout, points = its hierarchy,  */
+/*     num_points rows) down to `level` <= 15.  One thread per ray walks its   */
+/*     subtree depth-first; the result is the sequence of the reference's      */
+/*     level-by-level expansion: rays in input order, a ray's hits front to    */
+/*     back.  raytrace_count: the count walk, the scan of the counts, and the  */
+/*     one host read -- *host_total (HOST memory) = the number of hits; the    */
+/*     call synchronises the stream.  with_exit != 0: a hit also needs an exit */
+/*     depth > 0.  raytrace_emit (same arguments, the same workspace           */
+/*     untouched in between, total = *host_total): repeats the walk and writes */
+/*     nuggets (total, 2) int32 = (ray, point) and, depth_mode 1, depths       */
+/*     (total) float32 = entry, depth_mode 2, depths (total, 2) = entry, exit  */
+/*     (count must have run with with_exit != 0 exactly when depth_mode == 2). */
+/*     4 launches in all, whatever `level`.  workspace:                        */
+/*     kamd_spc_raytrace_workspace(N) bytes.  1 <= N < 2^31.  A node index is  */
+/*     compared with num_points, a byte index with num_bytes, an output row    */
+/*     with total: a failed comparison ends that branch / skips that write.    */
+/*   pack_scan: feats (n, C), boundaries (n) bytes (non-zero = the element     */
+/*     starts a pack; element 0 always does) -> out (n, C): the cumulative sum */
+/*     (prod != 0: product) inside every pack, sequentially in index order     */
+/*     (reverse: from the pack's end) in T; exclusive: the identity first.     */
+/*     One launch, no host read, no allocation: capturable.                    */
+/*   pack_reduce: inclusive_sum (n) int32 = the inclusive sum of boundaries    */
+/*     (element i belongs to pack inclusive_sum[i] - 1) -> out (num_packs, C), */
+/*     each row accumulated from the pack's first element on in index order:   */
+/*     no atomics, bit-identical run to run.  Rows no pack names are left      */
+/*     untouched.  One launch.                                                 */
+/* ------------------------------------------------------------------------- */
+size_t kamd_spc_raytrace_workspace(int64_t N);
+int kamd_spc_raytrace_count(void* stream, int64_t N, int level, int64_t num_bytes, int64_t num_points, const uint8_t* octree,
+                            const int32_t* exsum, const int16_t* points, const float* origin, const float* direction, int with_exit,
+                            void* workspace, int64_t* host_total);
+int kamd_spc_raytrace_emit(void* stream, int64_t N, int level, int64_t num_bytes, int64_t num_points, const uint8_t* octree,
+                           const int32_t* exsum, const int16_t* points, const float* origin, const float* direction, int depth_mode,
+                           const void* workspace, int64_t total, int32_t* nuggets, float* depths);
+int kamd_spc_pack_scan_f32(void* stream, int64_t n, int64_t C, const float* feats, const uint8_t* boundaries, int prod, int exclusive,
+                           int reverse, float* out);
+int kamd_spc_pack_scan_f64(void* stream, int64_t n, int64_t C, const double* feats, const uint8_t* boundaries, int prod,
+                           int exclusive, int reverse, double* out);
+int kamd_spc_pack_reduce_f32(void* stream, int64_t n, int64_t C, int64_t num_packs, const float* feats, const int32_t* inclusive_sum,
+                             int prod, float* out);
+int kamd_spc_pack_reduce_f64(void* stream, int64_t n, int64_t C, int64_t num_packs, const double* feats,
+                             const int32_t* inclusive_sum, int prod, double* out);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -7,6 +7,7 @@ module ``kaolin._C`` for the DIB-R / 3D-metrics hot path
     _C.metrics.sided_distance_forward_cuda       / sided_distance_backward_cuda
     _C.metrics.unbatched_triangle_distance_forward_cuda / _backward_cuda
     _C.render.sg.unbatched_reduced_sg_inner_product_forward_cuda / _backward_cuda
+    _C.render.spc.raytrace_cuda, cumsum_cuda / cumprod_cuda, sum_reduce_cuda / prod_reduce_cuda
 
 Same names, argument order, allocation/ownership rules and error strings; the work
 is done by hand-written HIP kernels in libkaolin_amd.so through the C ABI of

@@ -13,6 +13,8 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
     kaolin_amd.metrics.voxelgrid  iou
     kaolin_amd.metrics.tetmesh  tetrahedron_volume, equivolume, amips (fused HIP kernels, atomic-free reductions)
     kaolin_amd.render.lighting  spherical-gaussian (HIP reduced inner product) and spherical-harmonic shading
+    kaolin_amd.render.spc       unbatched_raytrace (HIP depth-first octree walk), mark_pack_boundaries, diff, cumsum, cumprod,
+                                sum_reduce, prod_reduce, exponential_integration (HIP pack scans and reductions)
     kaolin_amd._C               the 8 operator bindings of ``kaolin._C`` on this path
     kaolin_amd.distributed      batch/view sharding over RCCL (new; the reference has none)
 

@@ -85,7 +85,13 @@ SIGNATURES = {
     'kamd_spc_scan_workspace': (_sz, [_i64, _i64]),
     'kamd_spc_scan_octrees': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     'kamd_spc_generate_points': (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'kamd_spc_raytrace_workspace': (_sz, [_i64]),
+    'kamd_spc_raytrace_count': (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    'kamd_spc_raytrace_emit': (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _vp]),
 }
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_spc_pack_scan_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _i, _i, _i, _vp])
+    SIGNATURES[f'kamd_spc_pack_reduce_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i, _vp])
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_spc_query_multiscale_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp])
