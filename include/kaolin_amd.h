@@ -1036,6 +1036,75 @@ int kamd_spc_to_dense_backward_f64(void* stream, int64_t B, int64_t C, int level
                                    const int16_t* points, const int64_t* meta, const double* grad_grid, double* grad_features);
 
 /* ------------------------------------------------------------------------- */
+/* ops.spc feature grids: dual octree, trinkets, trilinear interpolation     */
+/* (reference: kaolin/ops/spc/spc.py make_dual / make_trinkets, points.py    */
+/* InterpolateTrilinear, point_utils_cuda.cu; csrc/spc_trilinear.hip).       */
+/*   dual_build: points = ONE point hierarchy (num_points rows), host_first  */
+/*     (HOST, max_level + 2 int64) = row 1 of its pyramid.  One key          */
+/*     level << 48 | Morton(corner) per (point, corner), ONE radix sort over */
+/*     the 3 (max_level + 1) code bits and the level bits, heads + scan, and */
+/*     the one host read: host_starts (HOST, max_level + 2 int64) = row 1 of */
+/*     the dual pyramid; the call synchronises the stream.  dual_emit then   */
+/*     writes the num_dual = host_starts[max_level + 1] int16 rows from the  */
+/*     same workspace (kamd_spc_dual_workspace bytes).  max_level <= 14: a   */
+/*     corner of level l reaches 2^l.                                        */
+/*   trinkets: (num_points, 8) int32, the index of every corner in its level */
+/*     of the dual, relative to the level; parents (num_points) int32, the   */
+/*     absolute index of point >> 1, -1 for the root.  host_first /          */
+/*     host_first_dual: row 1 of the two pyramids (HOST).  One launch, no    */
+/*     host read; a corner or parent that is not found is -1.                */
+/*   trilinear_coeffs: coords (n,3) in [-1,1], points (n,3) -> (n,8), corner */
+/*     order c000, c001, ... (z fastest).                                    */
+/*   interpolate: coords (N,S,3) float32, pidx (N) int32 (-1 = miss), points */
+/*     (num_points,3), trinkets (num_points,8), feats (num_feats,D) -> out   */
+/*     (N,S,D).  backward_feats accumulates with float atomics into a buffer */
+/*     it zeroes first (f16: `sums` is a float buffer of num_feats * D,      */
+/*     rounded once into grad_feats); backward_coords writes the derivative  */
+/*     by the LOCAL cell coordinate, (N,S,3) float32.  One launch each (two  */
+/*     and three with the fill and the rounding); no host read: capturable.  */
+/*     A pidx outside [0, num_points) or a trinket outside [0, num_feats) is */
+/*     a miss: zeros, no access.  trinkets must be 16-byte aligned.          */
+/* ------------------------------------------------------------------------- */
+size_t kamd_spc_dual_workspace(int64_t num_points, int max_level);
+int kamd_spc_dual_build(void* stream, int64_t num_points, int max_level, const int16_t* points, const int64_t* host_first,
+                        void* workspace, size_t workspace_bytes, int64_t* host_starts);
+int kamd_spc_dual_emit(void* stream, int64_t num_points, int max_level, const void* workspace, int64_t num_dual,
+                       int16_t* points_dual);
+int kamd_spc_trinkets(void* stream, int64_t num_points, int64_t num_dual, int max_level, const int16_t* points,
+                      const int16_t* points_dual, const int64_t* host_first, const int64_t* host_first_dual, int32_t* trinkets,
+                      int32_t* parents);
+int kamd_spc_trilinear_coeffs_f16(void* stream, int64_t n, int level, const void* coords, const int16_t* points, void* coeffs);
+int kamd_spc_trilinear_coeffs_f32(void* stream, int64_t n, int level, const float* coords, const int16_t* points, float* coeffs);
+int kamd_spc_trilinear_coeffs_f64(void* stream, int64_t n, int level, const double* coords, const int16_t* points, double* coeffs);
+int kamd_spc_interpolate_forward_f16(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                     const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                     const void* feats, void* out);
+int kamd_spc_interpolate_forward_f32(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                     const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                     const float* feats, float* out);
+int kamd_spc_interpolate_forward_f64(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                     const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                     const double* feats, double* out);
+int kamd_spc_interpolate_backward_feats_f16(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                            const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                            const void* grad_out, float* sums, void* grad_feats);
+int kamd_spc_interpolate_backward_feats_f32(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                            const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                            const float* grad_out, float* grad_feats);
+int kamd_spc_interpolate_backward_feats_f64(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                            const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                            const double* grad_out, double* grad_feats);
+int kamd_spc_interpolate_backward_coords_f16(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                             const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                             const void* feats, const void* grad_out, float* grad_coords);
+int kamd_spc_interpolate_backward_coords_f32(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                             const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                             const float* feats, const float* grad_out, float* grad_coords);
+int kamd_spc_interpolate_backward_coords_f64(void* stream, int64_t N, int64_t S, int64_t D, int level, int64_t num_points, int64_t num_feats,
+                                             const float* coords, const int32_t* pidx, const int16_t* points, const int32_t* trinkets,
+                                             const double* feats, const double* grad_out, float* grad_coords);
+
+/* ------------------------------------------------------------------------- */
 /* render.spc: octree ray tracing and the packed ray operators (reference:     */
 /* kaolin/csrc/render/spc; csrc/spc_raytrace.hip).                             */
 /*   raytrace: N rays (origin, direction (N,3) float32) through ONE octree     */

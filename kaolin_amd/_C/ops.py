@@ -823,6 +823,167 @@ def to_dense_backward(points, level, pyramid, features, grad_outputs):
     return _spc_to_dense('to_dense_backward', True, points, level, pyramid, features, grad_outputs)
 
 
+# ---- kaolin._C.ops.spc: feature grids on csrc/spc_trilinear.hip ------------------------------------------------------------
+SPC_DUAL_MAX_LEVEL = 14     # a corner of level l reaches 2^l: int16 and the 15-bit Morton codes hold it up to level 14
+
+
+def _spc_pyramid_row(fn, pyramid, what, rows):
+    """row 1 of a (2, max_level + 2) CPU pyramid as a ctypes int64 array, after checking that it starts at 0, does not decrease,
+    agrees with row 0 and ends at `rows`"""
+    torch_check(not pyramid.is_cuda and pyramid.dim() == 2 and pyramid.size(0) == 2 and pyramid.size(1) >= 2,
+                f'{fn}: {what} must be a CPU tensor of size {{2, max_level + 2}}')
+    count, first = pyramid[0].tolist(), pyramid[1].tolist()
+    L = len(first) - 2
+    if L > SPC_DUAL_MAX_LEVEL:
+        raise ValueError(f'{fn}: max_level {L}: the corners of level 15 reach 32768, which neither int16 nor the 15-bit Morton '
+                         f'codes hold; dual octrees go up to level {SPC_DUAL_MAX_LEVEL}')
+    if first[0] != 0 or first[L + 1] != rows or any(c < 0 or first[l] + c != first[l + 1] for l, c in enumerate(count[:L + 1])):
+        raise ValueError(f'{fn}: {what} does not describe the {rows} rows of its hierarchy: {pyramid.tolist()}')
+    return L, (ctypes.c_int64 * (L + 2))(*first)
+
+
+def make_dual_cuda(point_hierarchy, pyramid):
+    """ours (the reference builds the dual in Python, level by level): point_hierarchy (num_points, 3) int16 CUDA, pyramid (2,
+    max_level + 2) int32 CPU -> (point_hierarchy_dual (num_dual, 3) int16, pyramid_dual like pyramid).  All levels in one sort;
+    ONE host read (the level sizes): the call synchronises the current stream and cannot be captured in a graph."""
+    fn = 'make_dual_cuda'
+    _spc_points_arg(fn, point_hierarchy)
+    n, dev = point_hierarchy.size(0), point_hierarchy.device
+    L, first = _spc_pyramid_row(fn, pyramid, 'pyramid', n)
+    torch_check(n > 0, f'{fn}: no points')
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_spc_dual_workspace(n, L)
+        ws = _lib.workspace(nbytes, dev)
+        starts = (ctypes.c_int64 * (L + 2))()
+        _lib.check(lib.kamd_spc_dual_build(sp, n, L, _lib.ptr(point_hierarchy), ctypes.cast(first, ctypes.c_void_p), _lib.ptr(ws),
+                                           nbytes, ctypes.cast(starts, ctypes.c_void_p)), fn)
+        starts = list(starts)                                   # data-dependent sizes: the one host read
+        dual = torch.empty((starts[L + 1], 3), dtype=torch.int16, device=dev)
+        _lib.check(lib.kamd_spc_dual_emit(sp, n, L, _lib.ptr(ws), starts[L + 1], _lib.ptr(dual)), fn)
+    pyramid_dual = torch.tensor([[starts[l + 1] - starts[l] for l in range(L + 1)] + [0], starts], dtype=pyramid.dtype)
+    return dual, pyramid_dual
+
+
+def make_trinkets_cuda(point_hierarchy, pyramid, point_hierarchy_dual, pyramid_dual):
+    """ours (the reference looks Morton codes up in Python dictionaries): -> (trinkets (num_points, 8) int32: the index of every
+    corner in its level of the dual, relative to the level; parents (num_points) int32: absolute, -1 for the root).  One launch, no
+    host read, no allocation besides the results: capturable."""
+    fn = 'make_trinkets_cuda'
+    _spc_points_arg(fn, point_hierarchy)
+    _spc_points_arg(fn, point_hierarchy_dual)
+    torch_check(point_hierarchy.device == point_hierarchy_dual.device, f'{fn}: expected every tensor on the same device')
+    n, nd, dev = point_hierarchy.size(0), point_hierarchy_dual.size(0), point_hierarchy.device
+    L, first = _spc_pyramid_row(fn, pyramid, 'pyramid', n)
+    Ld, first_dual = _spc_pyramid_row(fn, pyramid_dual, 'pyramid_dual', nd)
+    torch_check(L == Ld, f'{fn}: pyramid and pyramid_dual differ in depth')
+    torch_check(n > 0, f'{fn}: no points')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        trinkets = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        parents = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(lib.kamd_spc_trinkets(_lib.stream_ptr(dev), n, nd, L, _lib.ptr(point_hierarchy), _lib.ptr(point_hierarchy_dual),
+                                         ctypes.cast(first, ctypes.c_void_p), ctypes.cast(first_dual, ctypes.c_void_p),
+                                         _lib.ptr(trinkets), _lib.ptr(parents)), fn)
+    return trinkets, parents
+
+
+def coords_to_trilinear_cuda(coords, points, level):
+    """reference: point_utils.cpp ``coords_to_trilinear_cuda``: coords (n, 3) half / float / double, points (n, 3) int16 -> (n, 8)
+    coefficients c000, c001, ... in coords' dtype.  Unlike the reference, coords are the NORMALISED coordinates in [-1, 1] and
+    ``level`` is an argument: the kernel evaluates ``2^level (c / 2 + 1 / 2) - p`` in double itself.  One launch, capturable."""
+    fn = 'coords_to_trilinear_cuda'
+    torch_check(coords.is_cuda and points.is_cuda, f'{fn}: coords and points must be CUDA tensors')
+    torch_check(coords.device == points.device, f'{fn}: expected every tensor on the same device')
+    torch_check(coords.dim() == 2 and coords.size(1) == 3 and coords.is_contiguous(), f'{fn}: coords must be contiguous, of size {{num_coords, 3}}')
+    torch_check(points.dtype == torch.int16 and tuple(points.shape) == tuple(coords.shape) and points.is_contiguous(),
+                f'{fn}: points must be a contiguous short tensor of the size of coords')
+    sfx = _lib.dtype_suffix(coords.dtype, fn, allowed=('f16', 'f32', 'f64'))
+    level = int(level)
+    torch_check(0 <= level <= SPC_MAX_LEVEL, f'{fn}: level must be in [0, {SPC_MAX_LEVEL}]')
+    lib = _lib.load()
+    with _lib.on_device(coords.device):
+        out = torch.empty((coords.size(0), 8), dtype=coords.dtype, device=coords.device)
+        _lib.check(getattr(lib, f'kamd_spc_trilinear_coeffs_{sfx}')(_lib.stream_ptr(coords.device), coords.size(0), level,
+                                                                  _lib.ptr(coords), _lib.ptr(points), _lib.ptr(out)), fn)
+    return out
+
+
+def _spc_interpolate_args(fn, coords, pidx, point_hierarchy, trinkets, feats, level, grad_out=None):
+    """the checks of the reference's interpolate_trilinear_cuda (point_utils.cpp) -> (suffix, N, S, D, level)"""
+    tensors = [coords, pidx, point_hierarchy, trinkets, feats] + ([grad_out] if grad_out is not None else [])
+    torch_check(all(x.is_cuda for x in tensors), f'{fn}: coords, pidx, point_hierarchy, trinkets and feats must be CUDA tensors')
+    torch_check(all(x.device == coords.device for x in tensors), f'{fn}: expected every tensor on the same device')
+    torch_check(all(x.is_contiguous() for x in tensors), f'{fn}: expected contiguous tensors')
+    torch_check(coords.dtype == torch.float32 and coords.dim() == 3 and coords.size(2) == 3 and coords.size(1) >= 1,
+                f'{fn}: coords must be a float tensor of size {{num_voxels, num_samples, 3}}')
+    torch_check(pidx.dtype == torch.int32 and pidx.dim() == 1 and pidx.size(0) == coords.size(0),
+                f'{fn}: pidx must be an int tensor of size {{num_voxels}}')
+    _spc_points_arg(fn, point_hierarchy)
+    torch_check(trinkets.dtype == torch.int32 and trinkets.dim() == 2 and trinkets.size(1) == 8 and
+                trinkets.size(0) == point_hierarchy.size(0), f'{fn}: trinkets must be an int tensor of size {{num_points, 8}}')
+    torch_check(trinkets.data_ptr() % 16 == 0, f'{fn}: trinkets must be 16-byte aligned')
+    torch_check(feats.dim() == 2 and feats.size(1) >= 1, f'{fn}: feats must be of size {{num_feats, feature_dim}}')
+    sfx = _lib.dtype_suffix(feats.dtype, fn, allowed=('f16', 'f32', 'f64'))
+    N, S, D = coords.size(0), coords.size(1), feats.size(1)
+    if grad_out is not None:
+        torch_check(grad_out.dtype == feats.dtype and tuple(grad_out.shape) == (N, S, D),
+                    f'{fn}: grad_output must be a {_lib.pretty_dtype(feats.dtype)} tensor of size {(N, S, D)}')
+    level = int(level)
+    torch_check(0 <= level <= SPC_MAX_LEVEL, f'{fn}: level must be in [0, {SPC_MAX_LEVEL}]')
+    return sfx, N, S, D, level
+
+
+def interpolate_trilinear_cuda(coords, pidx, point_hierarchy, trinkets, feats, level):
+    """reference: point_utils.cpp ``interpolate_trilinear_cuda``: coords (N, S, 3) float32 in [-1, 1], pidx (N) int32 (-1: a miss),
+    point_hierarchy (num_points, 3) int16, trinkets (num_points, 8) int32, feats (num_feats, D) half / float / double -> (N, S, D).
+    Lanes along D, a group of lanes per sample.  A pidx or a trinket out of range is a miss.  One launch, capturable."""
+    fn = 'interpolate_trilinear_cuda'
+    sfx, N, S, D, level = _spc_interpolate_args(fn, coords, pidx, point_hierarchy, trinkets, feats, level)
+    dev = coords.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.empty((N, S, D), dtype=feats.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_spc_interpolate_forward_{sfx}')(
+            _lib.stream_ptr(dev), N, S, D, level, point_hierarchy.size(0), feats.size(0), _lib.ptr(coords), _lib.ptr(pidx),
+            _lib.ptr(point_hierarchy), _lib.ptr(trinkets), _lib.ptr(feats), _lib.ptr(out)), fn)
+    return out
+
+
+def interpolate_trilinear_backward_feats_cuda(coords, pidx, point_hierarchy, trinkets, feats, level, grad_output):
+    """ours (the reference chains torch operators): -> grad_feats, of the size and dtype of feats.  One fused kernel: coefficients
+    recomputed, the samples of a voxel summed in registers, float (double for double) atomic adds into a zeroed buffer; half
+    accumulates in float32 and is rounded once.  Results may differ in the last bits from run to run.  Capturable."""
+    fn = 'interpolate_trilinear_backward_feats_cuda'
+    sfx, N, S, D, level = _spc_interpolate_args(fn, coords, pidx, point_hierarchy, trinkets, feats, level, grad_output)
+    dev = coords.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad = torch.empty_like(feats)
+        sums = torch.empty(feats.shape, dtype=torch.float32, device=dev) if sfx == 'f16' else None     # alive until after the call
+        extra = [_lib.ptr(sums)] if sums is not None else []
+        _lib.check(getattr(lib, f'kamd_spc_interpolate_backward_feats_{sfx}')(
+            _lib.stream_ptr(dev), N, S, D, level, point_hierarchy.size(0), feats.size(0), _lib.ptr(coords), _lib.ptr(pidx),
+            _lib.ptr(point_hierarchy), _lib.ptr(trinkets), _lib.ptr(grad_output), *extra, _lib.ptr(grad)), fn)
+    return grad
+
+
+def interpolate_trilinear_backward_coords_cuda(coords, pidx, point_hierarchy, trinkets, feats, level, grad_output):
+    """ours: -> (N, S, 3) float32, the derivative by the LOCAL cell coordinate (the reference's convention: no factor 2^(level - 1)).
+    Lanes along D, a reduction across the group of a sample.  One launch, capturable."""
+    fn = 'interpolate_trilinear_backward_coords_cuda'
+    sfx, N, S, D, level = _spc_interpolate_args(fn, coords, pidx, point_hierarchy, trinkets, feats, level, grad_output)
+    dev = coords.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad = torch.empty_like(coords)
+        _lib.check(getattr(lib, f'kamd_spc_interpolate_backward_coords_{sfx}')(
+            _lib.stream_ptr(dev), N, S, D, level, point_hierarchy.size(0), feats.size(0), _lib.ptr(coords), _lib.ptr(pidx),
+            _lib.ptr(point_hierarchy), _lib.ptr(trinkets), _lib.ptr(feats), _lib.ptr(grad_output), _lib.ptr(grad)), fn)
+    return grad
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
@@ -840,4 +1001,8 @@ spc = _types.SimpleNamespace(points_to_morton_cuda=points_to_morton_cuda, morton
                              morton_to_octree=morton_to_octree, scan_octrees_cuda=scan_octrees_cuda,
                              generate_points_cuda=generate_points_cuda, query_cuda=query_cuda,
                              query_multiscale_cuda=query_multiscale_cuda, to_dense_forward=to_dense_forward,
-                             to_dense_backward=to_dense_backward)
+                             to_dense_backward=to_dense_backward, make_dual_cuda=make_dual_cuda,
+                             make_trinkets_cuda=make_trinkets_cuda, coords_to_trilinear_cuda=coords_to_trilinear_cuda,
+                             interpolate_trilinear_cuda=interpolate_trilinear_cuda,
+                             interpolate_trilinear_backward_feats_cuda=interpolate_trilinear_backward_feats_cuda,
+                             interpolate_trilinear_backward_coords_cuda=interpolate_trilinear_backward_coords_cuda)

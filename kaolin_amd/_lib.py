@@ -89,6 +89,18 @@ SIGNATURES = {
     'kamd_spc_raytrace_count': (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'kamd_spc_raytrace_emit': (_i, [_vp, _i64, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _vp]),
 }
+SIGNATURES.update({
+    'kamd_spc_dual_workspace': (_sz, [_i64, _i]),
+    'kamd_spc_dual_build': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    'kamd_spc_dual_emit': (_i, [_vp, _i64, _i, _vp, _i64, _vp]),
+    'kamd_spc_trinkets': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+})
+for _t in ('f16', 'f32', 'f64'):
+    SIGNATURES[f'kamd_spc_trilinear_coeffs_{_t}'] = (_i, [_vp, _i64, _i, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_spc_interpolate_forward_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i, _i64, _i64] + [_vp] * 6)
+    SIGNATURES[f'kamd_spc_interpolate_backward_feats_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i, _i64, _i64] +
+                                                               [_vp] * (7 if _t == 'f16' else 6))
+    SIGNATURES[f'kamd_spc_interpolate_backward_coords_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i, _i64, _i64] + [_vp] * 7)
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_spc_pack_scan_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _i, _i, _i, _vp])
     SIGNATURES[f'kamd_spc_pack_reduce_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i, _vp])

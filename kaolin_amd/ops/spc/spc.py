@@ -1,5 +1,5 @@
-"""``kaolin.ops.spc`` octrees: scan, point generation, query, dense conversion (reference: kaolin/ops/spc/spc.py).  CUDA tensors run
-the HIP kernels of csrc/spc.hip through ``_C.ops.spc``; CPU tensors (which the reference rejects) run the ``_torch_*`` formulations
+"""``kaolin.ops.spc`` octrees: scan, point generation, query, dense conversion, dual octree and trinkets (reference:
+kaolin/ops/spc/spc.py).  CUDA tensors run the HIP kernels of csrc/spc.hip and csrc/spc_trilinear.hip through ``_C.ops.spc``; CPU tensors (which the reference rejects) run the ``_torch_*`` formulations
 of the same pipelines below -- device-agnostic, so tools/time_spc.py also runs them on the GPU as its yardstick.
 
 ``exsum`` is accepted in the current layout only: per octree the inclusive sum of the bit counts, ``num_bytes`` entries."""
@@ -9,11 +9,12 @@ import warnings
 import torch
 
 from ... import _C
-from ..._C.ops import finish_scan as _finish_scan
-from .points import morton_to_points
+from ..._C.ops import SPC_DUAL_MAX_LEVEL as _DUAL_MAX_LEVEL, finish_scan as _finish_scan
+from .points import _torch_morton_to_points, _torch_points_to_corners, _torch_points_to_morton, morton_to_points
 from .uint8 import bits_to_uint8, uint8_bits_sum, uint8_to_bits
 
-__all__ = ['feature_grids_to_spc', 'scan_octrees', 'generate_points', 'to_dense', 'unbatched_query', 'unbatched_get_level_points']
+__all__ = ['feature_grids_to_spc', 'scan_octrees', 'generate_points', 'to_dense', 'unbatched_query', 'unbatched_get_level_points',
+           'unbatched_make_dual', 'unbatched_make_trinkets']
 
 _MAX_LEVEL = 15
 _PYR = _MAX_LEVEL + 2
@@ -279,3 +280,104 @@ def feature_grids_to_spc(feature_grids, masks=None):
 def unbatched_get_level_points(point_hierarchy, pyramid, level):
     """point_hierarchy (num_points, 3) and pyramid (2, max_level + 2) of ONE octree -> the points of ``level``."""
     return point_hierarchy[pyramid[1, level]:pyramid[1, level + 1]]
+
+
+# ---- dual octree and trinkets ------------------------------------------------------------------------------------------------------
+def _check_dual_depth(fn, pyramid, what='pyramid'):
+    if pyramid.dim() != 2 or pyramid.size(0) != 2 or pyramid.size(1) < 2 or pyramid.is_cuda:
+        raise ValueError(f'{fn}: {what} must be a CPU tensor of size (2, max_level + 2), got {tuple(pyramid.shape)}')
+    max_level = pyramid.size(1) - 2
+    if max_level > _DUAL_MAX_LEVEL:
+        raise ValueError(f'{fn}: max_level {max_level}: the corners of level 15 reach 32768, which neither int16 nor the 15-bit '
+                         f'Morton codes hold (the reference wraps silently); dual octrees go up to level {_DUAL_MAX_LEVEL}')
+    return max_level
+
+
+def _check_hierarchy(fn, points, pyramid, what_points='point_hierarchy', what='pyramid'):
+    """What both devices' paths ask of a hierarchy and its pyramid (the shims of the HIP path repeat it): int16 (n, 3) points, at
+    least one, and a pyramid whose rows agree, start at 0, do not decrease and end at n.  -> max_level"""
+    max_level = _check_dual_depth(fn, pyramid, what)
+    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.int16:
+        raise ValueError(f'{fn}: {what_points} must be short, of size (num_points, 3), got {points.dtype} {tuple(points.shape)}')
+    n = points.size(0)
+    if n == 0:
+        raise ValueError(f'{fn}: no points in {what_points} (an octree has at least its root)')
+    count, first = pyramid[0].tolist(), pyramid[1].tolist()
+    if first[0] != 0 or first[max_level + 1] != n or \
+            any(c < 0 or first[l] + c != first[l + 1] for l, c in enumerate(count[:max_level + 1])):
+        raise ValueError(f'{fn}: {what} does not describe the {n} rows of {what_points}: {pyramid.tolist()}')
+    return max_level
+
+
+def _torch_make_dual(point_hierarchy, pyramid):
+    """Level by level: the Morton codes of the 8 corners of every point, unique (which sorts them), decoded."""
+    L = pyramid.size(1) - 2
+    first = pyramid[1].tolist()
+    levels = []
+    for l in range(L + 1):
+        corners = _torch_points_to_corners(point_hierarchy[first[l]:first[l + 1]]).reshape(-1, 3)
+        levels.append(_torch_morton_to_points(torch.unique(_torch_points_to_morton(corners))))
+    counts = [len(p) for p in levels]
+    pyramid_dual = torch.zeros_like(pyramid)
+    pyramid_dual[0, :L + 1] = torch.tensor(counts, dtype=pyramid.dtype)
+    pyramid_dual[1, 1:] = torch.cumsum(torch.tensor(counts), 0).to(pyramid.dtype)
+    return torch.cat(levels), pyramid_dual
+
+
+def unbatched_make_dual(point_hierarchy, pyramid):
+    """The dual of ONE octree: point_hierarchy (num_points, 3) int16 and pyramid (2, max_level + 2) int32 CPU -> (point_hierarchy_dual
+    (num_dual_points, 3) int16, pyramid_dual (2, max_level + 2), like pyramid): per level the distinct corners of the level's
+    cells (``points_to_corners``), in Morton order.  Features live on these corners; ``unbatched_make_trinkets`` maps cells to them.
+
+    A corner of level l reaches 2^l, so the deepest octree with a dual has ``max_level = 14``: deeper raises ValueError (the
+    reference wraps to -32768 silently).  On the GPU all levels go through ONE radix sort of ``level << 48 | Morton`` keys, and the
+    host reads the level sizes once (the reference: a unique and an argsort with their reads per level)."""
+    _check_hierarchy('unbatched_make_dual', point_hierarchy, pyramid)
+    if point_hierarchy.is_cuda:
+        return _C.ops.spc.make_dual_cuda(point_hierarchy.contiguous(), pyramid.contiguous())
+    return _torch_make_dual(point_hierarchy, pyramid)
+
+
+def _torch_make_trinkets(point_hierarchy, pyramid, point_hierarchy_dual, pyramid_dual):
+    """Level by level: the corners' Morton codes searched in the level's sorted dual codes, the parents' in the previous level's."""
+    dev = point_hierarchy.device
+    L = pyramid.size(1) - 2
+    first, first_dual = pyramid[1].tolist(), pyramid_dual[1].tolist()
+
+    def find(codes, sorted_codes):
+        if sorted_codes.numel() == 0:
+            return torch.full_like(codes, -1)
+        at = torch.searchsorted(sorted_codes, codes).clamp(max=sorted_codes.numel() - 1)
+        return torch.where(sorted_codes[at] == codes, at, -1)
+    trinkets, parents = [], []
+    for l in range(L + 1):
+        points = point_hierarchy[first[l]:first[l + 1]]
+        dual_codes = _torch_points_to_morton(point_hierarchy_dual[first_dual[l]:first_dual[l + 1]])
+        trinkets.append(find(_torch_points_to_morton(_torch_points_to_corners(points).reshape(-1, 3)), dual_codes).reshape(-1, 8))
+        if l == 0:
+            parents.append(torch.full((points.size(0),), -1, dtype=torch.long, device=dev))
+        else:
+            at = find(_torch_points_to_morton(points >> 1), _torch_points_to_morton(point_hierarchy[first[l - 1]:first[l]]))
+            parents.append(torch.where(at >= 0, at + first[l - 1], -1))
+    return torch.cat(trinkets).int(), torch.cat(parents).int()
+
+
+def unbatched_make_trinkets(point_hierarchy, pyramid, point_hierarchy_dual, pyramid_dual):
+    """The indirection from the cells of ONE octree to its dual (``unbatched_make_dual``) -> (trinkets (num_points, 8) int32,
+    parents (num_points) int32).
+
+    ``trinkets[i, j]`` is the index of corner j of point i (the corner order of ``points_to_corners``) in the dual, RELATIVE TO THE
+    START OF ITS LEVEL -- the reference's convention: a feature tensor with one row per dual point of a level is indexed by the
+    level's trinkets directly.  ``parents[i]`` is the absolute index in ``point_hierarchy`` of the parent ``point >> 1``, -1 for
+    the root.  A corner or parent that is not there (a dual that does not belong to the hierarchy) is -1.  On the GPU: one launch,
+    a binary search per (point, corner), no host read (the reference: Python dictionaries on the host)."""
+    fn = 'unbatched_make_trinkets'
+    if _check_hierarchy(fn, point_hierarchy, pyramid) != \
+            _check_hierarchy(fn, point_hierarchy_dual, pyramid_dual, 'point_hierarchy_dual', 'pyramid_dual'):
+        raise ValueError(f'{fn}: pyramid and pyramid_dual differ in depth')
+    if point_hierarchy.device != point_hierarchy_dual.device:
+        raise ValueError(f'{fn}: point_hierarchy is on {point_hierarchy.device}, point_hierarchy_dual on {point_hierarchy_dual.device}')
+    if point_hierarchy.is_cuda:
+        return _C.ops.spc.make_trinkets_cuda(point_hierarchy.contiguous(), pyramid.contiguous(), point_hierarchy_dual.contiguous(),
+                                             pyramid_dual.contiguous())
+    return _torch_make_trinkets(point_hierarchy, pyramid, point_hierarchy_dual, pyramid_dual)
