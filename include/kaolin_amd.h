@@ -1105,6 +1105,46 @@ int kamd_spc_interpolate_backward_coords_f64(void* stream, int64_t N, int64_t S,
                                              const double* feats, const double* grad_out, float* grad_coords);
 
 /* ------------------------------------------------------------------------- */
+/* ops.spc sparse convolutions (reference: kaolin/csrc/ops/spc/convolution*    */
+/* and minkowski_conv.cu; csrc/spc_conv.hip).  The whole batch at once, no     */
+/* host read, no atomics: bit-identical from run to run.                       */
+/*   conv_map: map (K, n) int32, map[k][i] = the packed row, among the         */
+/*     num_targets points of the target level of the batch, of the neighbour   */
+/*     of row i under kernel_vectors[k] ((K, 3) int16), or -1.  The n rows are */
+/*     the points of `row_level` of the B items.  transposed == 0: the target  */
+/*     level is row_level + jump and the neighbour of p is (p << jump) + v;    */
+/*     else it is row_level - jump and the neighbour is (p - v) >> jump, where */
+/*     p - v >= 0 in every component and divisible by 2^jump.  A neighbour     */
+/*     outside the grid is a miss.  meta (device, int64): the B + 1 prefix of  */
+/*     the rows per item, then 6 per item: first octree byte, octree bytes,    */
+/*     index in `points` of its first row point, index in ITS hierarchy of its */
+/*     first target point, its target points, packed row of its first target.  */
+/*     One thread per (k, row) walks the item's octree (exsum in the current   */
+/*     layout).  K <= 65535, K * n < 2^31.  One launch.                        */
+/*   conv_gather: Y (n, N) = sum_k A[map[k][i]] . W[k], A (a_rows, C), W       */
+/*     (K, C, N); transpose_w != 0: W is (K, N, C) and W[k]^T is used.  Misses */
+/*     and entries >= a_rows contribute nothing (the row is never fetched).    */
+/*     Every element of Y is stored exactly once.  One launch.                 */
+/*   conv_wgrad: grad_weight (K, cin, cout) = sum over the rows j with a       */
+/*     neighbour of X[j]^T . G[map[k][j]], X (n, cin), G (g_rows, cout): one   */
+/*     partial per (k, row slice) in the workspace                             */
+/*     (kamd_spc_conv_workspace(K, cin, cout, sizeof(T)) bytes, host only),    */
+/*     then the slices summed in index order.  Two launches.                   */
+/* ------------------------------------------------------------------------- */
+int kamd_spc_conv_map(void* stream, int transposed, int64_t B, int64_t K, int64_t n, int row_level, int jump, int64_t num_bytes,
+                      int64_t num_points, int64_t num_targets, const uint8_t* octrees, const int32_t* exsum, const int16_t* points,
+                      const int16_t* kernel_vectors, const int64_t* meta, int32_t* map);
+int kamd_spc_conv_gather_f32(void* stream, int64_t n, int64_t K, int64_t a_rows, int64_t C, int64_t N, int transpose_w,
+                             const int32_t* map, const float* A, const float* W, float* Y);
+int kamd_spc_conv_gather_f64(void* stream, int64_t n, int64_t K, int64_t a_rows, int64_t C, int64_t N, int transpose_w,
+                             const int32_t* map, const double* A, const double* W, double* Y);
+size_t kamd_spc_conv_workspace(int64_t K, int64_t cin, int64_t cout, int elem_bytes);
+int kamd_spc_conv_wgrad_f32(void* stream, int64_t n, int64_t K, int64_t g_rows, int64_t cin, int64_t cout, const int32_t* map,
+                            const float* X, const float* G, void* workspace, size_t workspace_bytes, float* grad_weight);
+int kamd_spc_conv_wgrad_f64(void* stream, int64_t n, int64_t K, int64_t g_rows, int64_t cin, int64_t cout, const int32_t* map,
+                            const double* X, const double* G, void* workspace, size_t workspace_bytes, double* grad_weight);
+
+/* ------------------------------------------------------------------------- */
 /* render.spc: octree ray tracing and the packed ray operators (reference:     */
 /* kaolin/csrc/render/spc; csrc/spc_raytrace.hip).                             */
 /*   raytrace: N rays (origin, direction (N,3) float32) through ONE octree     */

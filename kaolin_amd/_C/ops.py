@@ -984,6 +984,160 @@ def interpolate_trilinear_backward_coords_cuda(coords, pidx, point_hierarchy, tr
     return grad
 
 
+# ---- kaolin._C.ops.spc: sparse convolutions on csrc/spc_conv.hip -----------------------------------------------------------
+def spc_conv_check(fn, transposed, octrees, point_hierarchies, level, pyramids, exsum, input, weight, kernel_vectors, jump,
+                   bias=None, grad_output=None):
+    """What conv3d / conv_transpose3d ask of their arguments on every device, before anything runs (ValueError; the reference's are
+    asserts that are compiled out) -> (input level, output level).  ``level`` is the level of ``input``."""
+    if not isinstance(pyramids, torch.Tensor) or pyramids.is_cuda or pyramids.dim() != 3 or pyramids.size(1) != 2 or \
+            pyramids.size(2) < 2 or pyramids.is_floating_point():
+        raise ValueError(f'{fn}: pyramids must be an integer CPU tensor of size (batch_size, 2, max_level + 2)')
+    max_level = pyramids.size(2) - 2
+    level, jump = int(level), int(jump)
+    if max_level > SPC_MAX_LEVEL or pyramids.size(0) < 1:
+        raise ValueError(f'{fn}: pyramids of {pyramids.size(0)} octrees of max_level {max_level}; at most {SPC_MAX_LEVEL}')
+    if not 0 <= level <= max_level:
+        raise ValueError(f'{fn}: level {level} outside [0, max_level = {max_level}]')
+    if jump < 0:
+        raise ValueError(f'{fn}: jump must not be negative, got {jump}')
+    out_level = level + jump if transposed else level - jump
+    if not 0 <= out_level <= max_level:
+        raise ValueError(f'{fn}: level {level} and jump {jump} give the output level {out_level}, outside [0, max_level = {max_level}]')
+    p = pyramids.tolist()                # plain integers from here on: a few dozen of them, cheaper than tensor arithmetic
+    n_in, n_out = sum(item[0][level] for item in p), sum(item[0][out_level] for item in p)
+    if input.dim() != 2 or input.size(0) != n_in or input.size(1) < 1:
+        raise ValueError(f'{fn}: input must be of size ({n_in}, in_channels) for level {level}, got {tuple(input.shape)}')
+    if kernel_vectors.dim() != 2 or kernel_vectors.size(1) != 3 or kernel_vectors.dtype != torch.int16 or kernel_vectors.size(0) < 1:
+        raise ValueError(f'{fn}: kernel_vectors must be short, of size (num_weights, 3), got {kernel_vectors.dtype} '
+                         f'{tuple(kernel_vectors.shape)}')
+    K = kernel_vectors.size(0)
+    if weight.dim() != 3 or weight.size(0) != K or weight.size(1) != input.size(1) or weight.size(2) < 1:
+        raise ValueError(f'{fn}: weight must be of size ({K}, {input.size(1)}, out_channels), got {tuple(weight.shape)}')
+    if bias is not None and tuple(bias.shape) != (weight.size(2),):
+        raise ValueError(f'{fn}: bias must be of size ({weight.size(2)},), got {tuple(bias.shape)}')
+    if grad_output is not None and tuple(grad_output.shape) != (n_out, weight.size(2)):
+        raise ValueError(f'{fn}: grad_outputs must be of size {(n_out, weight.size(2))}, got {tuple(grad_output.shape)}')
+    named = [('octrees', octrees), ('point_hierarchies', point_hierarchies), ('exsum', exsum), ('input', input), ('weight', weight),
+             ('kernel_vectors', kernel_vectors)] + ([('bias', bias)] if bias is not None else []) + \
+        ([('grad_outputs', grad_output)] if grad_output is not None else [])
+    for name, x in named:
+        if x.device != input.device:
+            raise ValueError(f'{fn}: {name} is on {x.device}, input on {input.device}; pyramids alone stays on the CPU')
+    for name, x in named[4:5] + named[6:]:
+        if x.dtype != input.dtype:
+            raise ValueError(f'{fn}: {name} is {x.dtype}, input {input.dtype}: input, weight and bias must be of one dtype')
+    if not input.is_floating_point():
+        raise ValueError(f'{fn}: input must be floating point, got {input.dtype}')
+    if K * max(n_in, n_out) >= 2 ** 31:
+        raise ValueError(f'{fn}: {K} kernel vectors x {max(n_in, n_out)} points: the neighbour table must stay below 2^31 entries')
+    nbytes, npoints = sum(item[1][max_level] for item in p), sum(item[1][max_level + 1] for item in p)
+    if octrees.dim() != 1 or octrees.dtype != torch.uint8 or octrees.numel() != nbytes:
+        raise ValueError(f'{fn}: octrees must be a byte tensor of the {nbytes} bytes the pyramids describe, got {octrees.dtype} '
+                         f'{tuple(octrees.shape)}')
+    if point_hierarchies.dim() != 2 or point_hierarchies.size(1) != 3 or point_hierarchies.dtype != torch.int16 or \
+            point_hierarchies.size(0) != npoints:
+        raise ValueError(f'{fn}: point_hierarchies must be short, of the {npoints} points the pyramids describe, got '
+                         f'{point_hierarchies.dtype} {tuple(point_hierarchies.shape)}')
+    if exsum.dim() != 1 or exsum.numel() != nbytes or exsum.dtype != torch.int32:
+        raise ValueError(f'{fn}: exsum has {exsum.numel()} {exsum.dtype} entries for {nbytes} octree bytes; only the current layout '
+                         '(num_bytes int entries, inclusive sums) is accepted, not the legacy one with a leading 0 per octree')
+    return level, out_level
+
+
+def spc_conv_meta(pyramids, row_level, target_level):
+    """The per-item table of kamd_spc_conv_map (int64, CPU) for rows at ``row_level`` and neighbours at ``target_level``."""
+    p = pyramids.tolist()
+    L = len(p[0][0]) - 2
+    prefix, per_item = [0], []
+    first_byte = first_point = first_target = 0
+    for count, first in p:
+        prefix.append(prefix[-1] + count[row_level])
+        per_item += [first_byte, first[L], first_point + first[row_level], first[target_level], count[target_level], first_target]
+        first_byte, first_point, first_target = first_byte + first[L], first_point + first[L + 1], first_target + count[target_level]
+    return torch.tensor(prefix + per_item, dtype=torch.long)
+
+
+def _spc_conv(fn, transposed, backward, octree, points, level, pyramid, exsum, inputs, grad_outputs, params, kernel_vectors, jump,
+              needs=(True, True)):
+    """The four convolution operators.  ``level`` is the level of ``inputs`` for a forward and -- as in the reference -- the
+    level of the OUTPUT (what the forward returned) for a backward.  One neighbour map per call: the forward's is indexed by the
+    output rows, the backward's by the input rows (the same triples, read the other way round), so both gradients are gathers."""
+    tensors = [octree, points, exsum, inputs, params, kernel_vectors] + ([grad_outputs] if backward else [])
+    torch_check(all(x.is_cuda for x in tensors), f'{fn}: octree, points, exsum, inputs, params and kernel_vectors must be CUDA tensors')
+    jump = int(jump)
+    if jump < 0:
+        raise ValueError(f'{fn}: jump must not be negative, got {jump}')
+    in_level = int(level) if not backward else (int(level) - jump if transposed else int(level) + jump)
+    in_level, out_level = spc_conv_check(fn, transposed, octree, points, in_level, pyramid, exsum, inputs, params, kernel_vectors,
+                                         jump, grad_output=grad_outputs if backward else None)
+    sfx = _lib.dtype_suffix(inputs.dtype, fn)
+    torch_check(all(x.is_contiguous() for x in tensors), f'{fn}: expected contiguous tensors')
+    torch_check(pyramid.size(0) <= 65535, f'{fn}: more than 65535 octrees in a batch')
+    K, cin, cout = params.shape
+    torch_check(K <= 65535, f'{fn}: more than 65535 kernel vectors')
+    counts = pyramid[:, 0].tolist()
+    n_in, n_out = sum(c[in_level] for c in counts), sum(c[out_level] for c in counts)
+    dev = inputs.device
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        # forward: rows = outputs, neighbours = inputs; backward: rows = inputs, neighbours = outputs, the other mode
+        row_level, target_level, n, targets = (in_level, out_level, n_in, n_out) if backward else (out_level, in_level, n_out, n_in)
+        mode = int(transposed) ^ int(backward)
+        meta = spc_conv_meta(pyramid, row_level, target_level).to(dev)
+        table = torch.empty((K, n), dtype=torch.int32, device=dev)
+        _lib.check(lib.kamd_spc_conv_map(sp, mode, pyramid.size(0), K, n, row_level, jump, octree.numel(), points.size(0), targets,
+                                         _lib.ptr(octree), _lib.ptr(exsum), _lib.ptr(points), _lib.ptr(kernel_vectors),
+                                         _lib.ptr(meta), _lib.ptr(table)), fn)
+        gather = getattr(lib, f'kamd_spc_conv_gather_{sfx}')
+        if not backward:
+            out = torch.empty((n_out, cout), dtype=inputs.dtype, device=dev)
+            _lib.check(gather(sp, n_out, K, n_in, cin, cout, 0, _lib.ptr(table), _lib.ptr(inputs), _lib.ptr(params), _lib.ptr(out)), fn)
+            return out, out_level
+        grad_inputs = grad_params = None
+        if needs[0]:
+            grad_inputs = torch.empty_like(inputs)
+            _lib.check(gather(sp, n_in, K, n_out, cout, cin, 1, _lib.ptr(table), _lib.ptr(grad_outputs), _lib.ptr(params),
+                              _lib.ptr(grad_inputs)), fn)
+        if needs[1]:
+            grad_params = torch.empty_like(params)
+            nbytes = lib.kamd_spc_conv_workspace(K, cin, cout, inputs.element_size())
+            ws = _lib.workspace(nbytes, dev)
+            _lib.check(getattr(lib, f'kamd_spc_conv_wgrad_{sfx}')(sp, n_in, K, n_out, cin, cout, _lib.ptr(table), _lib.ptr(inputs),
+                                                                 _lib.ptr(grad_outputs), _lib.ptr(ws), nbytes, _lib.ptr(grad_params)), fn)
+    return [grad_inputs, grad_params]
+
+
+def Conv3d_forward(octree, points, level, pyramid, exsum, inputs, params, kernel_vectors, jump):
+    """reference: convolution.cpp ``Conv3d_forward``: inputs (points of ``level`` in the batch, in), params (K, in, out),
+    kernel_vectors (K, 3) int16 -> (outputs (points of level - jump, out), level - jump).  Two launches (neighbour map,
+    gather-GEMM) for the whole batch, no host read, no atomics (the reference: per item a scan, a compaction, K host reads and a
+    kernel per offset that adds with float atomics)."""
+    return _spc_conv('Conv3d_forward', False, False, octree, points, level, pyramid, exsum, inputs, None, params, kernel_vectors, jump)
+
+
+def Conv3d_backward(octree, points, level, pyramid, exsum, inputs, grad_outputs, params, kernel_vectors, jump, needs=(True, True)):
+    """reference: convolution.cpp ``Conv3d_backward``: ``level`` is the forward's OUTPUT level -> [grad_inputs, grad_params].
+    Four launches (transposed map over the input rows, gather-GEMM with W^T, weight gradient, its finishing sum); ``needs`` (ours)
+    skips a gradient nobody asked for (None in its place)."""
+    return _spc_conv('Conv3d_backward', False, True, octree, points, level, pyramid, exsum, inputs, grad_outputs, params,
+                     kernel_vectors, jump, needs)
+
+
+def ConvTranspose3d_forward(octree, points, level, pyramid, exsum, inputs, params, kernel_vectors, jump):
+    """reference: convolution.cpp ``ConvTranspose3d_forward``: -> (outputs (points of level + jump, out), level + jump)."""
+    return _spc_conv('ConvTranspose3d_forward', True, False, octree, points, level, pyramid, exsum, inputs, None, params,
+                     kernel_vectors, jump)
+
+
+def ConvTranspose3d_backward(octree, points, level, pyramid, exsum, inputs, grad_outputs, params, kernel_vectors, jump,
+                             needs=(True, True)):
+    """reference: convolution.cpp ``ConvTranspose3d_backward``: ``level`` is the forward's OUTPUT level -> [grad_inputs,
+    grad_params]; the direct map over the (coarse) input rows."""
+    return _spc_conv('ConvTranspose3d_backward', True, True, octree, points, level, pyramid, exsum, inputs, grad_outputs, params,
+                     kernel_vectors, jump, needs)
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
@@ -1005,4 +1159,6 @@ spc = _types.SimpleNamespace(points_to_morton_cuda=points_to_morton_cuda, morton
                              make_trinkets_cuda=make_trinkets_cuda, coords_to_trilinear_cuda=coords_to_trilinear_cuda,
                              interpolate_trilinear_cuda=interpolate_trilinear_cuda,
                              interpolate_trilinear_backward_feats_cuda=interpolate_trilinear_backward_feats_cuda,
-                             interpolate_trilinear_backward_coords_cuda=interpolate_trilinear_backward_coords_cuda)
+                             interpolate_trilinear_backward_coords_cuda=interpolate_trilinear_backward_coords_cuda,
+                             Conv3d_forward=Conv3d_forward, Conv3d_backward=Conv3d_backward,
+                             ConvTranspose3d_forward=ConvTranspose3d_forward, ConvTranspose3d_backward=ConvTranspose3d_backward)

@@ -8,7 +8,9 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
                                 voxelgrids_to_cubic_meshes (sort-free HIP pipeline)
     kaolin_amd.ops.mesh         subdivide_tetmesh (HIP edge-midpoint pipeline), inverse_vertices_offset, check_sign,
                                 subdivide_trianglemesh (Loop subdivision with a per-vertex alpha, HIP pipeline)
-    kaolin_amd.ops.spc          the SPC core: scan_octrees, generate_points, unbatched_query, to_dense, unbatched_points_to_octree (HIP)
+    kaolin_amd.ops.spc          the SPC core: scan_octrees, generate_points, unbatched_query, to_dense, unbatched_points_to_octree (HIP),
+                                conv3d / conv_transpose3d and their layers (HIP neighbour map + MFMA gather-GEMM)
+    kaolin_amd.rep              Spc, the structured point cloud data class
     kaolin_amd.ops.voxelgrid    fill (HIP flood fill over bit grids), downsample, extract_surface, extract_odms, project_odms
     kaolin_amd.metrics.voxelgrid  iou
     kaolin_amd.metrics.tetmesh  tetrahedron_volume, equivolume, amips (fused HIP kernels, atomic-free reductions)
@@ -24,7 +26,7 @@ existing notebooks/tests written against the reference import it unchanged.
 import sys
 
 from . import _C  # noqa: F401
-from . import io, metrics, ops, render, utils  # noqa: F401
+from . import io, metrics, ops, render, rep, utils  # noqa: F401
 from . import distributed  # noqa: F401
 
 __version__ = '0.1.0'

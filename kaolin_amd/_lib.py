@@ -104,6 +104,13 @@ for _t in ('f16', 'f32', 'f64'):
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_spc_pack_scan_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _i, _i, _i, _vp])
     SIGNATURES[f'kamd_spc_pack_reduce_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i, _vp])
+SIGNATURES.update({
+    'kamd_spc_conv_map': (_i, [_vp, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i64] + [_vp] * 6),
+    'kamd_spc_conv_workspace': (_sz, [_i64, _i64, _i64, _i]),
+})
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_spc_conv_gather_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_spc_conv_wgrad_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp])
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_spc_query_multiscale_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp])

@@ -217,9 +217,12 @@ def to_dense(point_hierarchies, pyramids, input, level=-1, **kwargs):
     int32 CPU of a batch, input (points of ``level`` in the batch, C) -> (B, C, 2^level, 2^level, 2^level), ``out[b, :, x, y, z] =
     input[i]`` for point i = (x, y, z) of item b, zero elsewhere.  ``level = -1`` is the deepest level.  Differentiable in
     ``input``.  float32 / float64 CUDA tensors run in HIP (a zero fill and one thread per (point, channel); the backward is the
-    matching gather), everything else the torch formulation.  Any other keyword raises TypeError."""
-    if kwargs:
-        raise TypeError(f'to_dense got an unexpected keyword argument {next(iter(kwargs))!r}')
+    matching gather), everything else the torch formulation.  The other members of ``Spc.KEYS`` are accepted and ignored, so that
+    ``to_dense(**spc.to_dict(), input=..., level=...)`` works; any other keyword raises TypeError."""
+    from ...rep.spc import Spc
+    unexpected = kwargs.keys() - Spc.KEYS
+    if unexpected:
+        raise TypeError(f'to_dense got an unexpected keyword argument {list(unexpected)[0]!r}')
     max_level = pyramids.shape[2] - 2
     if level < 0:
         level = max_level + 1 + level
