@@ -629,6 +629,52 @@ int kamd_mesh_to_spc_results(void* stream, int64_t n, int level, const float* fa
                              uint8_t* octree, int64_t* face_ids, float* barycoords);
 
 /* ------------------------------------------------------------------------- */
+/* ops.conversions.gs_to_spc_cuda(means3D, scales, rotations, iso, tol, level) */
+/*     -> [points int16 (N, 3), gaus_id int64 (N), pack_boundary bool (N),     */
+/*         cov3d_invs float (G, 6)]                                            */
+/* ops.conversions.integrate_gs_cuda(points, gaus_id, means3D, cov3d_invs,     */
+/*     opacities, level, step) -> float (N)                                    */
+/* (reference: kaolin/csrc/ops/conversions/gs_to_spc/gs_to_spc.cpp,            */
+/* gs_to_spc_cuda.cu:146-804).  means3D (G,3), scales (G,3), rotations (G,4)   */
+/* float32.  One (voxel, Gaussian) pair per voxel of `level` that the iso       */
+/* ellipsoid of a Gaussian overlaps, ordered by (Morton code, Gaussian id).     */
+/* The host sequence (the library never allocates):                            */
+/*  1. prepare: cov3d_invs (G,6) and `prepared` (prepare_workspace(G) bytes:    */
+/*     AABB and contact points of every Gaussian).                             */
+/*  2. proposals = (Morton code 0, Gaussian g) for every g; level_from = 0,     */
+/*     tested = 0 (the root is tested too).  stage_count(level_from, level_to = */
+/*     min(level_from + stage_levels(), level)): counts + offsets (n + 1,       */
+/*     offsets[n] = total, read by the host); stage_emit writes the `total`     */
+/*     surviving pairs at level_to (no slot >= total is written); repeat from   */
+/*     level_to with tested = 1 until level_to == level.                        */
+/*  3. finish: stable sort by code on 3 * level bits, points, gaus_id and       */
+/*     pack_boundary (one byte per pair: 1 at the first pair of a voxel).       */
+/* integrate_gs is ONE launch and reads nothing back (graph-capturable); a      */
+/* gaus_id outside [0, G) integrates to 0.  1 <= step <= 1024.                  */
+/* ------------------------------------------------------------------------- */
+int kamd_gs_to_spc_stage_levels(void);
+size_t kamd_gs_to_spc_prepare_workspace(int64_t G);
+int kamd_gs_to_spc_prepare(void* stream, int64_t G, const float* means3D, const float* scales,
+                           const float* rotations, float iso, float tol, int level, float* cov3d_invs,
+                           void* prepared);
+size_t kamd_gs_to_spc_scan_workspace(int64_t n);
+int kamd_gs_to_spc_stage_count(void* stream, int64_t n, int64_t G, const float* means3D, const float* cov3d_invs,
+                               const void* prepared, float iso, const int64_t* morton, const int64_t* gaus_id,
+                               int level_from, int level_to, int tested, int32_t* counts, int64_t* offsets,
+                               void* scan_workspace);
+int kamd_gs_to_spc_stage_emit(void* stream, int64_t n, int64_t G, const float* means3D, const float* cov3d_invs,
+                              const void* prepared, float iso, const int64_t* morton, const int64_t* gaus_id,
+                              int level_from, int level_to, int tested, const int64_t* offsets, int64_t total,
+                              int64_t* morton_out, int64_t* gaus_id_out);
+size_t kamd_gs_to_spc_finish_workspace(int64_t n);
+int kamd_gs_to_spc_finish(void* stream, int64_t n, int level, const int64_t* morton, const int64_t* gaus_id,
+                          void* workspace, size_t workspace_bytes, int16_t* points, int64_t* gaus_id_out,
+                          uint8_t* pack_boundary);
+int kamd_integrate_gs(void* stream, int64_t n, int64_t G, const int16_t* points, const int64_t* gaus_id,
+                      const float* means3D, const float* cov3d_invs, const float* opacities, int level, int step,
+                      float* values);
+
+/* ------------------------------------------------------------------------- */
 /* ops.mesh.unbatched_mesh_intersection_cuda(points, v1, v2, v3) -> result     */
 /* (reference: kaolin/csrc/ops/mesh/mesh_intersection.cpp,  */
 /* mesh_intersection_cuda.cu:101-253).  points (N,3); v1,v2,v3 (F,3) = the      */

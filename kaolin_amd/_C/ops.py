@@ -154,6 +154,124 @@ def mesh_to_spc_cuda(face_vertices, level):
     return [octree, face_ids, bary]
 
 
+def _gs_float_args(fn, named):
+    """float32, one device, contiguous"""
+    for name, t in named:
+        torch_check(t.dtype == torch.float32, f'{fn}: expected scalar type Float for {name} but found ' + _lib.pretty_dtype(t.dtype))
+        torch_check(t.is_contiguous(), f'{fn}: {name} must be contiguous')
+
+
+def _gs_one_device(fn, named):
+    devices = {t.device for _, t in named}
+    torch_check(len(devices) == 1, f'{fn}: expected every tensor on one device, got {[str(t.device) for _, t in named]}')
+    return next(iter(devices))
+
+
+def _gs_level(fn, level):
+    level = int(level)
+    torch_check(0 <= level <= 15, f'{fn}: level must be in [0, 15]')
+    return level
+
+
+def gs_to_spc_cuda(means3D, scales, rotations, iso, tol, level):
+    """reference: kaolin/csrc/ops/conversions/gs_to_spc/gs_to_spc.cpp (``_C.ops.conversions.gs_to_spc_cuda``): means3D (G,3),
+    scales (G,3), rotations (G,4) float32 -> [points int16 (N,3), gaus_id int64 (N), pack_boundary bool (N), cov3d_invs float (G,6)]:
+    one pair per (voxel of ``level``, Gaussian whose iso ellipsoid overlaps it and all its ancestors), ordered by (Morton code,
+    Gaussian id); pack_boundary marks the first pair of every voxel.  No pair (G = 0 included): N = 0 and cov3d_invs still (G, 6).
+
+    Launches: 1 (prepare) + 4 per stage of three levels (count, two of the scan, emit; max(1, ceil(level / 3)) stages) + 4 per
+    sort pass (ceil(3 level / 8) passes; one copy at level 0) + 2 (run heads, points); one host read per stage: not capturable.  CPU tensors run the torch formulation of kaolin_amd/ops/conversions/gaussians.py (the same integer results)."""
+    fn = 'gs_to_spc_cuda'
+    named = (('means3D', means3D), ('scales', scales), ('rotations', rotations))
+    _gs_float_args(fn, named)
+    dev = _gs_one_device(fn, named)
+    G = means3D.size(0) if means3D.dim() > 0 else -1
+    torch_check(list(means3D.shape) == [G, 3], f'{fn}: means3D must be of size {{num_gaussians, 3}}, got {list(means3D.shape)}')
+    torch_check(list(scales.shape) == [G, 3], f'{fn}: scales must be of size {{num_gaussians, 3}}, got {list(scales.shape)}')
+    torch_check(list(rotations.shape) == [G, 4], f'{fn}: rotations must be of size {{num_gaussians, 4}}, got {list(rotations.shape)}')
+    level = _gs_level(fn, level)
+    iso, tol = float(iso), float(tol)
+    if not means3D.is_cuda:
+        from ..ops.conversions.gaussians import gs_to_spc_torch
+        return gs_to_spc_torch(means3D, scales, rotations, iso, tol, level)
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    depth = lib.kamd_gs_to_spc_stage_levels()
+    with _lib.on_device(dev):
+        cov = torch.empty((G, 6), dtype=torch.float32, device=dev)
+
+        def empty_result():
+            return [torch.empty((0, 3), dtype=torch.int16, device=dev), torch.empty(0, dtype=torch.long, device=dev),
+                    torch.empty(0, dtype=torch.bool, device=dev), cov]
+
+        if G == 0:
+            return empty_result()
+        prep = torch.empty(lib.kamd_gs_to_spc_prepare_workspace(G), dtype=torch.uint8, device=dev)
+        _lib.check(lib.kamd_gs_to_spc_prepare(sp, G, _lib.ptr(means3D), _lib.ptr(scales), _lib.ptr(rotations), iso, tol, level,
+                                              _lib.ptr(cov), _lib.ptr(prep)), fn)
+        n = G
+        morton = torch.zeros(n, dtype=torch.long, device=dev)
+        gid = torch.arange(n, dtype=torch.long, device=dev)
+        level_from, tested = 0, 0
+        while True:
+            level_to = min(level_from + depth, level)
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            offsets = torch.empty(n + 1, dtype=torch.long, device=dev)
+            scan_ws = torch.empty(lib.kamd_gs_to_spc_scan_workspace(n), dtype=torch.uint8, device=dev)
+            head = (sp, n, G, _lib.ptr(means3D), _lib.ptr(cov), _lib.ptr(prep), iso, _lib.ptr(morton), _lib.ptr(gid), level_from,
+                    level_to, tested)
+            _lib.check(lib.kamd_gs_to_spc_stage_count(*head, _lib.ptr(counts), _lib.ptr(offsets), _lib.ptr(scan_ws)), fn)
+            total = int(offsets[n].item())                     # data-dependent size: one host read per stage
+            if total == 0:
+                return empty_result()
+            morton_out = torch.empty(total, dtype=torch.long, device=dev)
+            gid_out = torch.empty(total, dtype=torch.long, device=dev)
+            _lib.check(lib.kamd_gs_to_spc_stage_emit(*head, _lib.ptr(offsets), total, _lib.ptr(morton_out), _lib.ptr(gid_out)), fn)
+            morton, gid, n = morton_out, gid_out, total
+            if level_to == level:
+                break
+            level_from, tested = level_to, 1
+        nbytes = lib.kamd_gs_to_spc_finish_workspace(n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        points = torch.empty((n, 3), dtype=torch.int16, device=dev)
+        gaus_id = torch.empty(n, dtype=torch.long, device=dev)
+        boundary = torch.empty(n, dtype=torch.bool, device=dev)
+        _lib.check(lib.kamd_gs_to_spc_finish(sp, n, level, _lib.ptr(morton), _lib.ptr(gid), _lib.ptr(ws), nbytes, _lib.ptr(points),
+                                             _lib.ptr(gaus_id), _lib.ptr(boundary)), fn)
+    return [points, gaus_id, boundary, cov]
+
+
+def integrate_gs_cuda(points, gaus_id, means3D, cov3d_invs, opacities, level, step):
+    """reference: gs_to_spc.cpp (``_C.ops.conversions.integrate_gs_cuda``): points int16 (N,3), gaus_id int64 (N), means3D (G,3),
+    cov3d_invs (G,6), opacities (G) or (G,1) float32 -> float32 (N): opacity times the mean of exp(-q / 2) over ``step``^3 samples of
+    the voxel, accumulated in float64 in a fixed order (the same bits every run).  One launch, no host read: capturable."""
+    fn = 'integrate_gs_cuda'
+    floats = (('means3D', means3D), ('cov3d_invs', cov3d_invs), ('opacities', opacities))
+    _gs_float_args(fn, floats)
+    torch_check(points.dtype == torch.int16, f'{fn}: expected scalar type Short for points but found ' + _lib.pretty_dtype(points.dtype))
+    torch_check(gaus_id.dtype == torch.long, f'{fn}: expected scalar type Long for gaus_id but found ' + _lib.pretty_dtype(gaus_id.dtype))
+    torch_check(points.is_contiguous() and gaus_id.is_contiguous(), f'{fn}: points and gaus_id must be contiguous')
+    dev = _gs_one_device(fn, (('points', points), ('gaus_id', gaus_id)) + floats)
+    N = points.size(0) if points.dim() > 0 else -1
+    G = means3D.size(0) if means3D.dim() > 0 else -1
+    torch_check(list(points.shape) == [N, 3], f'{fn}: points must be of size {{num_pairs, 3}}, got {list(points.shape)}')
+    torch_check(list(gaus_id.shape) == [N], f'{fn}: gaus_id must be of size {{num_pairs}}, got {list(gaus_id.shape)}')
+    torch_check(list(means3D.shape) == [G, 3], f'{fn}: means3D must be of size {{num_gaussians, 3}}, got {list(means3D.shape)}')
+    torch_check(list(cov3d_invs.shape) == [G, 6], f'{fn}: cov3d_invs must be of size {{num_gaussians, 6}}, got {list(cov3d_invs.shape)}')
+    torch_check(opacities.numel() == G, f'{fn}: {opacities.numel()} opacities for {G} Gaussians')
+    level, step = _gs_level(fn, level), int(step)
+    torch_check(1 <= step <= 1024, f'{fn}: step must be in [1, 1024]')
+    if not points.is_cuda:
+        from ..ops.conversions.gaussians import integrate_gs_torch
+        return integrate_gs_torch(points, gaus_id, means3D, cov3d_invs, opacities, level, step)
+    with _lib.on_device(dev):
+        values = torch.empty(N, dtype=torch.float32, device=dev)
+        if N > 0:
+            _lib.check(_lib.load().kamd_integrate_gs(_lib.stream_ptr(dev), N, G, _lib.ptr(points), _lib.ptr(gaus_id), _lib.ptr(means3D),
+                                                     _lib.ptr(cov3d_invs), _lib.ptr(opacities), level, step, _lib.ptr(values)), fn)
+    return values
+
+
 _FILL_SUFFIX = {torch.bool: 'u8', torch.uint8: 'u8', torch.int32: 'i32', torch.int64: 'i64', torch.float16: 'f16',
                 torch.float32: 'f32', torch.float64: 'f64'}
 
@@ -1149,7 +1267,8 @@ mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_in
                               tetmesh_midpoints_backward_cuda=tetmesh_midpoints_backward_cuda)
 conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
                                      marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda,
-                                     voxelgrids_to_cubic_meshes_cuda=voxelgrids_to_cubic_meshes_cuda)
+                                     voxelgrids_to_cubic_meshes_cuda=voxelgrids_to_cubic_meshes_cuda,
+                                     gs_to_spc_cuda=gs_to_spc_cuda, integrate_gs_cuda=integrate_gs_cuda)
 spc = _types.SimpleNamespace(points_to_morton_cuda=points_to_morton_cuda, morton_to_points_cuda=morton_to_points_cuda,
                              points_to_corners_cuda=points_to_corners_cuda, points_to_octree=points_to_octree,
                              morton_to_octree=morton_to_octree, scan_octrees_cuda=scan_octrees_cuda,

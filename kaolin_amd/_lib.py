@@ -108,6 +108,17 @@ SIGNATURES.update({
     'kamd_spc_conv_map': (_i, [_vp, _i, _i64, _i64, _i64, _i, _i, _i64, _i64, _i64] + [_vp] * 6),
     'kamd_spc_conv_workspace': (_sz, [_i64, _i64, _i64, _i]),
 })
+SIGNATURES.update({
+    'kamd_gs_to_spc_stage_levels': (_i, []),
+    'kamd_gs_to_spc_prepare_workspace': (_sz, [_i64]),
+    'kamd_gs_to_spc_prepare': (_i, [_vp, _i64, _vp, _vp, _vp, _f, _f, _i, _vp, _vp]),
+    'kamd_gs_to_spc_scan_workspace': (_sz, [_i64]),
+    'kamd_gs_to_spc_stage_count': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'kamd_gs_to_spc_stage_emit': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    'kamd_gs_to_spc_finish_workspace': (_sz, [_i64]),
+    'kamd_gs_to_spc_finish': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'kamd_integrate_gs': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+})
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_spc_conv_gather_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_spc_conv_wgrad_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp])

@@ -12,8 +12,8 @@
 //     are tested at once, the survivors of each depth kept as bits of one word), so proposals are materialised every
 //     third level only; each stage is a count
 //     pass, a scan and an emit pass (the host reads one number per stage: output sizes are data-dependent);
-//   * pairs leave a stage ordered by (triangle, Morton code); a stable radix sort on the 3*level key bits (the kernels
-//     below, 8 bits a pass; the reference calls thrust) then makes "first of every run" the smallest triangle of every voxel;
+//   * pairs leave a stage ordered by (triangle, Morton code); a stable radix sort on the 3*level key bits (spc_stage.h,
+//     8 bits a pass; the reference calls thrust) then makes "first of every run" the smallest triangle of every voxel;
 //   * run heads, compaction, ALL octree levels and their sizes are produced on the device into one workspace; the host
 //     reads the level sizes once, allocates the three results and a last kernel gathers them.
 // Voxel tests use the reference's expressions in its operand order (float differences, double projections, comparison
@@ -24,6 +24,7 @@
 #include "common.h"
 #include "profile.h"
 #include "spc_octree.h"
+#include "spc_stage.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
@@ -103,157 +104,20 @@ __device__ __forceinline__ bool ms_test(const MsTri& t, int x, int y, int z, int
   return ms_triangle_voxel(t, c, half);
 }
 
-// ---- a stage: every proposal (voxel at level_from, triangle) walks its subtree down to level_to -------------------------
-// EMIT = false: counts[i] = number of voxels at level_to that pass with all their ancestors;
-// EMIT = true : writes them (ascending Morton code) at offsets[i].  `tested` = the proposal's own level passed already.
-// Eight lanes share a proposal: they test the eight children of the current node at once (one ballot), then the group
-// descends into the survivors in child order, keeping the not-yet-visited children of each depth as 8 bits of one word.
-// All groups of a wavefront run the same loop; a group that is done idles until the last one finishes.
-template <bool EMIT>
-__global__ __launch_bounds__(256) void ms_stage_kernel(int64_t n, const float* __restrict__ fv,
-                                                       const int64_t* __restrict__ morton, const int64_t* __restrict__ tri,
-                                                       int level_from, int level_to, int tested, int* __restrict__ counts,
-                                                       const int64_t* __restrict__ offsets, int64_t* __restrict__ morton_out,
-                                                       int64_t* __restrict__ tri_out) {
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t i = gid >> 3;
-  const int k = (int)(gid & 7), grp = (threadIdx.x & 63) >> 3;
-  bool active = i < n;
-  int64_t t = 0, o = 0;
-  MsTri T = {};
-  int cx = 0, cy = 0, cz = 0, count = 0, d = 0;
-  unsigned rem = 0;  // 8 bits per depth: children still to visit
-  bool expand = false;
-  if (active) {
-    t = tri[i];
-    T = ms_load_tri(fv, t);
-    ms_to_point((uint64_t)morton[i], &cx, &cy, &cz);
-    if (EMIT) o = offsets[i];
-    const bool self = tested || ms_test(T, cx, cy, cz, level_from);
-    if (!self) {
-      active = false;
-    } else if (level_from == level_to) {
-      if (EMIT && k == 0) {
-        morton_out[o] = morton[i];
-        tri_out[o] = t;
-      }
-      count = 1;
-      active = false;
-    } else {
-      expand = true;
-    }
+// ---- a stage: every proposal (voxel at level_from, triangle) walks its subtree down to level_to: spc_stage_kernel of spc_stage.h
+// (eight lanes per proposal, three levels in registers) with the triangle as its primitive.  The stable radix sort of (Morton code,
+// triangle) pairs by code is spc_sort_pairs of the same header (the reference sorts with thrust, mesh_to_spc_cuda.cu:388-392): equal
+// codes keep their order -- triangles ascending inside a voxel, which is what picks a voxel's face.
+struct MsPrim {
+  typedef MsTri Data;
+  const float* fv;
+  __device__ __forceinline__ bool load(int64_t id, Data* d) const {
+    *d = ms_load_tri(fv, id);
+    return true;
   }
-  while (__any(active)) {
-    bool pass = false;
-    int nx = 0, ny = 0, nz = 0;
-    const int nl = level_from + d + 1;
-    if (active && expand) {
-      nx = 2 * cx + (k >> 2);
-      ny = 2 * cy + ((k >> 1) & 1);
-      nz = 2 * cz + (k & 1);
-      pass = ms_test(T, nx, ny, nz, nl);
-    }
-    const unsigned long long bal = __ballot(pass);
-    if (active) {
-      if (expand) {
-        unsigned mask = (unsigned)((bal >> (8 * grp)) & 0xFFull);
-        if (nl == level_to) {
-          if (EMIT && pass) {
-            const int64_t q = o + count + __popc(mask & ((1u << k) - 1u));
-            morton_out[q] = (int64_t)ms_to_morton(nx, ny, nz);
-            tri_out[q] = t;
-          }
-          count += __popc(mask);
-          mask = 0;
-        }
-        rem = (rem & ~(0xFFu << (8 * d))) | (mask << (8 * d));
-        expand = false;
-      }
-      const unsigned todo = (rem >> (8 * d)) & 0xFFu;
-      if (todo != 0u) {  // descend into the next surviving child
-        const int c = __builtin_ctz(todo);
-        rem &= ~(1u << (8 * d + c));
-        cx = 2 * cx + (c >> 2);
-        cy = 2 * cy + ((c >> 1) & 1);
-        cz = 2 * cz + (c & 1);
-        ++d;
-        expand = true;
-      } else if (d == 0) {
-        active = false;
-      } else {  // back to the parent
-        --d;
-        cx >>= 1;
-        cy >>= 1;
-        cz >>= 1;
-      }
-    }
-  }
-  if (!EMIT && i < n && k == 0) counts[i] = count;
-}
-
-// ---- stable LSD radix sort of (Morton code, triangle) pairs by code, 8 bits a pass ---------------------------------------
-// The reference sorts with thrust (mesh_to_spc_cuda.cu:388-392); here: per pass a digit histogram per block of 2 048 pairs, ONE
-// exclusive scan over the (digit, block) counts (ms_scan) and a scatter that ranks the pairs of a block in their original order
-// (wavefront by wavefront: the lanes sharing a digit are found with eight ballots, lower lanes first; wavefronts and rounds of 256
-// in order through LDS counters), so equal codes keep their order -- triangles ascending inside a voxel, which is what picks a
-// voxel's face.  No library, nothing but launches on the stream.
-constexpr int MS_SORT_ITEMS = 8, MS_SORT_BLOCK = 256 * MS_SORT_ITEMS;
-__global__ __launch_bounds__(256) void ms_sort_hist_kernel(int64_t n, const uint64_t* __restrict__ keys, int shift, int nblk,
-                                                           int* __restrict__ hist) {
-  __shared__ int s_h[256];
-  s_h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * MS_SORT_BLOCK;
-#pragma unroll
-  for (int r = 0; r < MS_SORT_ITEMS; ++r) {
-    const int64_t e = base + r * 256 + threadIdx.x;
-    if (e < n) atomicAdd(&s_h[(int)((keys[e] >> shift) & 255u)], 1);
-  }
-  __syncthreads();
-  hist[(size_t)threadIdx.x * nblk + blockIdx.x] = s_h[threadIdx.x];
-}
-__global__ __launch_bounds__(256) void ms_sort_scatter_kernel(int64_t n, const uint64_t* __restrict__ keys,
-                                                              const int64_t* __restrict__ vals, int shift, int nblk,
-                                                              const int64_t* __restrict__ offs, uint64_t* __restrict__ keys_out,
-                                                              int64_t* __restrict__ vals_out) {
-  __shared__ long long s_run[256];
-  __shared__ int s_wc[4][256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  s_run[tid] = offs[(size_t)tid * nblk + blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) s_wc[w][tid] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * MS_SORT_BLOCK;
-  for (int r = 0; r < MS_SORT_ITEMS; ++r) {
-    const int64_t e = base + r * 256 + tid;
-    const bool on = e < n;
-    const uint64_t key = on ? keys[e] : 0ull;
-    const int64_t val = on ? vals[e] : 0;
-    const int digit = (int)((key >> shift) & 255u);
-    // the lanes of this wavefront that hold the same digit (and a pair at all)
-    unsigned long long peers = __ballot(on);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const unsigned long long m = __ballot((digit >> bit) & 1);
-      peers &= ((digit >> bit) & 1) ? m : ~m;
-    }
-    const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-    if (on && rank == 0) s_wc[wave][digit] = __popcll(peers);
-    __syncthreads();
-    if (on) {
-      long long pos = s_run[digit] + rank;
-      for (int w = 0; w < wave; ++w) pos += s_wc[w][digit];
-      keys_out[pos] = key;
-      vals_out[pos] = val;
-    }
-    __syncthreads();
-    s_run[tid] += (s_wc[0][tid] + s_wc[1][tid]) + (s_wc[2][tid] + s_wc[3][tid]);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) s_wc[w][tid] = 0;
-    __syncthreads();
-  }
-}
-inline int ms_sort_blocks(int64_t n) { return (int)((n > 0 ? n : 1) + MS_SORT_BLOCK - 1) / MS_SORT_BLOCK; }
+  __device__ __forceinline__ bool test(const Data& d, int x, int y, int z, int level) const { return ms_test(d, x, y, z, level); }
+};
+constexpr int64_t MS_NO_TOTAL = INT64_MAX;  // the emit pass writes exactly the slots the count pass summed
 
 // after the sort: one voxel (its first, i.e. smallest, triangle) per run of equal codes; sizes[0] = voxels
 __global__ __launch_bounds__(256) void ms_unique_kernel(int64_t n, const int64_t* __restrict__ m, const int64_t* __restrict__ t,
@@ -357,7 +221,7 @@ MsWs ms_ws(void* base, int64_t n, int level) {
   w.sums = (int64_t*)take(((size_t)n / 1024 + 2) * 8);
   w.flag = (int*)take((size_t)(n > 0 ? n : 1) * 4);
   w.level_bytes = (unsigned char*)take((size_t)(level > 0 ? level : 1) * (size_t)(n > 0 ? n : 1));
-  const size_t hn = (size_t)256 * (size_t)ms_sort_blocks(n);
+  const size_t hn = spc_sort_hist_entries(n);
   w.sort_hist = (int*)take(hn * 4);
   w.sort_offs = (int64_t*)take((hn + 1) * 8);
   w.sort_sums = (int64_t*)take((hn / 1024 + 2) * 8);
@@ -380,8 +244,9 @@ int kamd_mesh_to_spc_stage_count(void* stream, int64_t n, const float* face_vert
   if (level_from < 0 || level_to < level_from || level_to > MS_MAX_LEVEL) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   kamd::ProfScope prof_(kamd::K_SPC_STAGE, st);
-  hipLaunchKernelGGL(ms_stage_kernel<false>, dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, face_vertices, morton, triangle_id,
-                     level_from, level_to, tested, counts, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr);
+  hipLaunchKernelGGL((spc_stage_kernel<false, MsPrim>), dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, MsPrim{face_vertices}, morton,
+                     triangle_id, level_from, level_to, tested, counts, (const int64_t*)nullptr, MS_NO_TOTAL, (int64_t*)nullptr,
+                     (int64_t*)nullptr);
   return ms_scan(st, n, nullptr, counts, offsets, (int64_t*)scan_workspace);
 }
 
@@ -391,8 +256,8 @@ int kamd_mesh_to_spc_stage_emit(void* stream, int64_t n, const float* face_verti
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   kamd::ProfScope prof_(kamd::K_SPC_STAGE, st);
-  hipLaunchKernelGGL(ms_stage_kernel<true>, dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, face_vertices, morton, triangle_id,
-                     level_from, level_to, tested, (int*)nullptr, offsets, morton_out, triangle_id_out);
+  hipLaunchKernelGGL((spc_stage_kernel<true, MsPrim>), dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, MsPrim{face_vertices}, morton,
+                     triangle_id, level_from, level_to, tested, (int*)nullptr, offsets, MS_NO_TOTAL, morton_out, triangle_id_out);
   KAMD_RETURN_LAST_ERROR();
 }
 
@@ -407,30 +272,10 @@ int kamd_mesh_to_spc_build(void* stream, int64_t n, int level, const int64_t* mo
   const MsWs w = ms_ws(workspace, n, level);
   if (workspace == nullptr || workspace_bytes < w.total_bytes) return (int)hipErrorInvalidValue;
   kamd::ProfScope prof_(kamd::K_SPC_BUILD, st);
-  {
-    // (level 0: a single voxel, every key is 0 and the order is already by triangle -- one pass over no bits would do; a copy)
-    const int passes = (3 * level + 7) / 8;
-    const int nblk = ms_sort_blocks(n);
-    const uint64_t* src_k = (const uint64_t*)morton;
-    const int64_t* src_v = triangle_id;
-    if (passes == 0) {
-      unsigned cg = (unsigned)kamd_cdiv(n, 256);
-      if (cg > (unsigned)KAMD_NUM_CU * 8u) cg = (unsigned)KAMD_NUM_CU * 8u;
-      hipLaunchKernelGGL(ms_copy_words_kernel, dim3(cg), dim3(256), 0, st, n, morton, w.sm, triangle_id, w.st);
-    }
-    for (int k = 0; k < passes; ++k) {  // the last pass lands in (sm, st); (um, ut) is the other side
-      const bool to_sorted = ((passes - 1 - k) & 1) == 0;
-      uint64_t* dst_k = (uint64_t*)(to_sorted ? w.sm : w.um);
-      int64_t* dst_v = to_sorted ? w.st : w.ut;
-      hipLaunchKernelGGL(ms_sort_hist_kernel, dim3(nblk), dim3(256), 0, st, n, src_k, 8 * k, nblk, w.sort_hist);
-      KAMD_CHECK(ms_scan(st, (int64_t)256 * nblk, nullptr, w.sort_hist, w.sort_offs, w.sort_sums));
-      hipLaunchKernelGGL(ms_sort_scatter_kernel, dim3(nblk), dim3(256), 0, st, n, src_k, src_v, 8 * k, nblk,
-                         (const int64_t*)w.sort_offs, dst_k, dst_v);
-      src_k = dst_k;
-      src_v = dst_v;
-    }
-    KAMD_CHECK(hipGetLastError());
-  }
+  // the sorted pairs land in (sm, st); (um, ut) is the other side of the ping-pong.  (level 0: a single voxel, every key is 0 and
+  // the order is already by triangle: a copy)
+  KAMD_CHECK(spc_sort_pairs(st, n, 3 * level, (const uint64_t*)morton, triangle_id, (uint64_t*)w.um, w.ut, (uint64_t*)w.sm, w.st,
+                            SpcSortWs{w.sort_hist, w.sort_offs, w.sort_sums}));
   const unsigned g = (unsigned)kamd_cdiv(n, 256);
   hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)nullptr, (const int64_t*)w.sm, 0, w.flag);
   KAMD_CHECK(ms_scan(st, n, nullptr, w.flag, w.pos, w.sums));

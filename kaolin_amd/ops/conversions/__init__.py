@@ -4,3 +4,5 @@ from .tetmesh import marching_tetrahedra  # noqa: F401
 from . import tetmesh  # noqa: F401
 from .voxelgrid import voxelgrids_to_cubic_meshes  # noqa: F401
 from . import voxelgrid  # noqa: F401
+from .gaussians import gs_to_voxelgrid  # noqa: F401
+from . import gaussians  # noqa: F401
