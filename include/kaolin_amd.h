@@ -1238,6 +1238,72 @@ int kamd_spc_pack_reduce_f64(void* stream, int64_t n, int64_t C, int64_t num_pac
                              const int32_t* inclusive_sum, int prod, double* out);
 
 /* ------------------------------------------------------------------------- */
+/* ops.spc Bayesian-fusion reconstruction (csrc/spc_bf.hip): the operators of  */
+/* the reference's bf.cpp / recon.cpp, the empty-aware query of query.cpp, and */
+/* bf_cells (no reference counterpart).  One thread per point, node or pixel;  */
+/* no atomics.  float32 arithmetic, one rounding per operation, no FMA,        */
+/* correctly rounded divide and square root (DESIGN.md has the contract).      */
+/*   T16: the 16 floats (host memory, row major) of T = M * cam.               */
+/*   mip: (mip_size, 2) floats, coarsest level first; level l starts at        */
+/*     (h >> L)(w >> L)(4^l - 1) / 3.  h and w are multiples of 2^L.            */
+/*   build_mip2d with true_depth converts depth IN PLACE (pixels equal to      */
+/*     max_depth stay).  L launches.                                           */
+/*   oracle / oracle_final: level 0 answers occupancy 1, state 2.              */
+/*   inclusive_sum: workspace of kamd_spc_bf_scan_workspace(n) bytes.          */
+/*   subdivide / compactify / compactify_nodes: pass = the scan's last entry,  */
+/*     read by the caller; a slot outside [0, pass) is skipped.                */
+/*   process_final_voxels: the pointers are those of the tail to write;        */
+/*     nvsum entries are compared with prev_size.                              */
+/*   merge / merge_empty / query: the walk compares every node index with      */
+/*     num_bytes (octree, empty and exsum have num_bytes entries each) and a   */
+/*     row of probs / colors with rows; a failed comparison answers empty.     */
+/*   query: >= 0 the point index, -1 empty or outside, -2 - depth unseen.      */
+/*   cells_count: every cell of `level` that query does not answer with -1 is  */
+/*     counted (level + 3 launches); host2 = {K, bytes the levels account      */
+/*     for}: the one host read.  cells_emit: the K cells (K, 3) int16 in       */
+/*     ascending Morton order, one thread per cell, from the same workspace    */
+/*     (kamd_spc_bf_cells_workspace(num_bytes) bytes).                         */
+/* ------------------------------------------------------------------------- */
+int64_t kamd_spc_bf_mip_size(int h, int w, int mip_levels);
+int kamd_spc_bf_build_mip2d(void* stream, int h, int w, int mip_levels, float fx, float fy, float cx, float cy, float max_depth,
+                            int true_depth, float* depth, float* mip);
+int kamd_spc_bf_oracle(void* stream, int64_t n, const int16_t* points, int level, const float* T16, float sigma, const float* depth,
+                       int h, int w, int mip_levels, const float* mip, int32_t* occupancy, int32_t* state);
+int kamd_spc_bf_oracle_final(void* stream, int64_t n, const int16_t* points, int level, const float* T16, float sigma,
+                             const float* depth, int h, int w, int32_t* occupancy, int32_t* state, float* probabilities);
+int kamd_spc_bf_colors_final(void* stream, int64_t n, const int16_t* points, const float* T16, float sigma, const float* image,
+                             const float* depth, int h, int w, const float* probabilities, uint8_t* colors, float* normals);
+size_t kamd_spc_bf_scan_workspace(int64_t n);
+int kamd_spc_bf_inclusive_sum(void* stream, int64_t n, const int32_t* in, int32_t* out, void* workspace);
+int kamd_spc_bf_subdivide(void* stream, int64_t n, int64_t pass, const int16_t* points, const int32_t* insum, int16_t* new_points,
+                          int32_t* nvsum);
+int kamd_spc_bf_compactify(void* stream, int64_t n, int64_t pass, const int16_t* points, const int32_t* insum, int16_t* new_points,
+                           int64_t* nvsum);
+int kamd_spc_bf_process_final_voxels(void* stream, int64_t num_nodes, const int32_t* state, const int32_t* nvsum, int64_t prev_size,
+                                     int32_t* occupancies, int32_t* prev_state, uint8_t* octree, uint8_t* empty);
+int kamd_spc_bf_compactify_nodes(void* stream, int64_t n, int64_t pass, const int32_t* insum, const uint8_t* octree, const uint8_t* empty,
+                                 uint8_t* new_octree, uint8_t* new_empty);
+int kamd_spc_bf_merge_empty(void* stream, int64_t n, const int16_t* points, int level, int64_t num_bytes0, int64_t num_bytes1,
+                            const uint8_t* octree0, const uint8_t* octree1, const uint8_t* empty0, const uint8_t* empty1,
+                            const int32_t* exsum0, const int32_t* exsum1, int32_t* occupancy, int32_t* state);
+int kamd_spc_bf_merge(void* stream, int64_t n, const int16_t* points, int level, int64_t num_bytes0, int64_t num_bytes1,
+                      const uint8_t* octree0, const uint8_t* octree1, const uint8_t* empty0, const uint8_t* empty1, const int32_t* exsum0,
+                      const int32_t* exsum1, int64_t offset0, int64_t offset1, int64_t rows0, int64_t rows1, const float* probs0,
+                      const float* probs1, const uint8_t* colors0, const uint8_t* colors1, int32_t* occupancy, int32_t* state,
+                      float* probabilities, uint8_t* colors);
+int kamd_spc_bf_query_f16(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree, const uint8_t* empty,
+                          const int32_t* exsum, const void* coords, int32_t* out);
+int kamd_spc_bf_query_f32(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree, const uint8_t* empty,
+                          const int32_t* exsum, const float* coords, int32_t* out);
+int kamd_spc_bf_query_f64(void* stream, int64_t Q, int level, int64_t num_bytes, const uint8_t* octree, const uint8_t* empty,
+                          const int32_t* exsum, const double* coords, int32_t* out);
+size_t kamd_spc_bf_cells_workspace(int64_t num_bytes);
+int kamd_spc_bf_cells_count(void* stream, int64_t num_bytes, int level, const uint8_t* octree, const uint8_t* empty, void* workspace,
+                            int64_t* host2);
+int kamd_spc_bf_cells_emit(void* stream, int64_t num_bytes, int level, const uint8_t* octree, const uint8_t* empty, const void* workspace,
+                           int64_t K, int16_t* cells);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

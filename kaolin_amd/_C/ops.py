@@ -1256,6 +1256,366 @@ def ConvTranspose3d_backward(octree, points, level, pyramid, exsum, inputs, grad
                      kernel_vectors, jump, needs)
 
 
+# ---- kaolin._C.ops.spc: Bayesian-fusion reconstruction on csrc/spc_bf.hip ----------------------------------------------------------
+def _bf_need(fn, cond, msg):
+    if not cond:
+        raise ValueError(f'{fn}: {msg}')
+
+
+def _bf_tensor(fn, t, name, dtype, cols=None, cuda=True):
+    _bf_need(fn, isinstance(t, torch.Tensor) and t.dtype == dtype, f'{name} must be a {_lib.pretty_dtype(dtype)} tensor')
+    _bf_need(fn, t.is_cuda == cuda, f'{name} must be a {"CUDA" if cuda else "CPU"} tensor')
+    _bf_need(fn, t.is_contiguous(), f'{name} must be contiguous')
+    if cols is None:
+        _bf_need(fn, t.dim() == 1, f'{name} must be 1D, got {tuple(t.shape)}')
+    else:
+        _bf_need(fn, t.dim() == 2 and t.size(1) == cols, f'{name} must be of size (n, {cols}), got {tuple(t.shape)}')
+
+
+def _bf_same_device(fn, *tensors):
+    _bf_need(fn, len({t.device for t in tensors}) == 1, 'expected every CUDA tensor on the same device')
+
+
+def _bf_level(fn, level):
+    level = int(level)
+    _bf_need(fn, 0 <= level <= SPC_MAX_LEVEL, f'level must be in [0, {SPC_MAX_LEVEL}], got {level}')
+    return level
+
+
+def bf_transform(cam, level):
+    """T = M * cam as 16 float32 (numpy, row major): M = diag(s, s, s, 1) with last row (-1, -1, -1, 1), s = 2^(1 - level); every
+    element is the sum over k = 0..3, in that order, of float32 products (the arithmetic contract)."""
+    import numpy as np
+    c = cam.detach().cpu().numpy().astype(np.float32).reshape(4, 4)
+    s = np.float32(2.0 ** (1 - level))
+    M = np.array([[s, 0, 0, 0], [0, s, 0, 0], [0, 0, s, 0], [-1, -1, -1, 1]], dtype=np.float32)
+    T = np.zeros((4, 4), dtype=np.float32)
+    with np.errstate(all='ignore'):         # (a non-finite cam is the caller's to refuse)
+        for i in range(4):
+            for j in range(4):
+                acc = M[i, 0] * c[0, j]
+                for k in range(1, 4):
+                    acc = np.float32(acc + np.float32(M[i, k] * c[k, j]))
+                T[i, j] = acc
+    return T
+
+
+def _bf_cam(fn, cam, level):
+    _bf_need(fn, isinstance(cam, torch.Tensor) and tuple(cam.shape) == (4, 4) and cam.dtype == torch.float32,
+             'cam must be a float tensor of size (4, 4)')
+    T = bf_transform(cam, level)
+    _bf_need(fn, bool(torch.isfinite(cam).all()) and bool(torch.isfinite(torch.from_numpy(T)).all()),
+             'cam, and its product with the level\'s scaling, must be finite')
+    return (ctypes.c_float * 16)(*[float(v) for v in T.reshape(-1)])
+
+
+def _bf_depth(fn, depth_map):
+    _bf_need(fn, isinstance(depth_map, torch.Tensor) and depth_map.dtype == torch.float32 and depth_map.dim() == 2,
+             'depth_map must be a float tensor of size (height, width)')
+    _bf_need(fn, depth_map.is_cuda and depth_map.is_contiguous(), 'depth_map must be a contiguous CUDA tensor')
+    _bf_need(fn, depth_map.numel() > 0, 'depth_map is empty')
+    return depth_map.size(0), depth_map.size(1)
+
+
+def _bf_mip_size(fn, h, w, mip_levels):
+    mip_levels = int(mip_levels)
+    size = _lib.load().kamd_spc_bf_mip_size(h, w, mip_levels)
+    _bf_need(fn, size >= 0, f'mip_levels must be in [1, 15] and divide the {h} x {w} depth map into whole 2^mip_levels blocks, '
+                            f'got {mip_levels}')
+    return mip_levels, size
+
+
+def build_mip2d(depth_map, intrinsics, mip_levels, max_depth, true_depth):
+    """reference: recon.cpp ``build_mip2d``: depth_map (h, w) float CUDA, intrinsics (4, 4) float (fx, fy at [0, 0], [1, 1]; cx, cy
+    at [2, 0], [2, 1]) -> the min / max pyramid (size, 2), coarsest level first.  With ``true_depth`` depth_map is converted IN PLACE
+    from ray length to z depth (pixels equal to max_depth stay).  mip_levels launches, capturable."""
+    fn = 'build_mip2d'
+    h, w = _bf_depth(fn, depth_map)
+    mip_levels, size = _bf_mip_size(fn, h, w, mip_levels)
+    _bf_need(fn, isinstance(intrinsics, torch.Tensor) and tuple(intrinsics.shape) == (4, 4), 'intrinsics must be of size (4, 4)')
+    k = intrinsics.detach().cpu().float().reshape(-1).tolist()
+    _bf_need(fn, k[0] != 0.0 and k[5] != 0.0, 'the focal lengths must not be zero')
+    lib, dev = _lib.load(), depth_map.device
+    with _lib.on_device(dev):
+        mip = torch.empty((size, 2), dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_spc_bf_build_mip2d(_lib.stream_ptr(dev), h, w, mip_levels, k[0], k[5], k[8], k[9], float(max_depth),
+                                               int(bool(true_depth)), _lib.ptr(depth_map), _lib.ptr(mip)), fn)
+    return mip
+
+
+def oracleB(points, level, sigma, cam, depth_map, mips, mip_levels):
+    """reference: bf.cpp ``oracleB``: points (n, 3) short of ``level`` against the depth pyramid -> (occupancy, state) int32 (n):
+    state 0 empty, 1 unseen, 2 occupied; occupancy 1 = keep and split.  One launch, capturable."""
+    fn = 'oracleB'
+    _bf_tensor(fn, points, 'points', torch.int16, 3)
+    level = _bf_level(fn, level)
+    h, w = _bf_depth(fn, depth_map)
+    mip_levels, size = _bf_mip_size(fn, h, w, mip_levels)
+    _bf_tensor(fn, mips, 'mips', torch.float32, 2)
+    _bf_need(fn, mips.size(0) == size, f'mips has {mips.size(0)} rows, a {h} x {w} map with {mip_levels} levels has {size}')
+    _bf_same_device(fn, points, depth_map, mips)
+    _bf_need(fn, float(sigma) != 0.0, "sigma can't be zero")
+    T = _bf_cam(fn, cam, level)
+    lib, dev, n = _lib.load(), points.device, points.size(0)
+    with _lib.on_device(dev):
+        occ = torch.empty(n, dtype=torch.int32, device=dev)
+        state = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(lib.kamd_spc_bf_oracle(_lib.stream_ptr(dev), n, _lib.ptr(points), level, ctypes.cast(T, ctypes.c_void_p), float(sigma),
+                                          _lib.ptr(depth_map), h, w, mip_levels, _lib.ptr(mips), _lib.ptr(occ), _lib.ptr(state)), fn)
+    return occ, state
+
+
+def oracleB_final(points, level, sigma, cam, depth_map):
+    """reference: bf.cpp ``oracleB_final``: the profile curve at the eight corners of every point -> (occupancy, state,
+    probabilities (n) float: the curve at corner 0).  One launch, capturable."""
+    fn = 'oracleB_final'
+    _bf_tensor(fn, points, 'points', torch.int16, 3)
+    level = _bf_level(fn, level)
+    h, w = _bf_depth(fn, depth_map)
+    _bf_same_device(fn, points, depth_map)
+    _bf_need(fn, float(sigma) != 0.0, "sigma can't be zero")
+    T = _bf_cam(fn, cam, level)
+    lib, dev, n = _lib.load(), points.device, points.size(0)
+    with _lib.on_device(dev):
+        occ = torch.empty(n, dtype=torch.int32, device=dev)
+        state = torch.empty(n, dtype=torch.int32, device=dev)
+        probs = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_spc_bf_oracle_final(_lib.stream_ptr(dev), n, _lib.ptr(points), level, ctypes.cast(T, ctypes.c_void_p),
+                                                float(sigma), _lib.ptr(depth_map), h, w, _lib.ptr(occ), _lib.ptr(state),
+                                                _lib.ptr(probs)), fn)
+    return occ, state, probs
+
+
+def colorsB_final(points, level, cam, sigma, image, depth_map, probabilities):
+    """reference: bf.cpp ``colorsB_final``: -> (colors (n, 4) uint8 in B, G, R, 0 order, normals (n, 3) float).  A normal that is
+    not finite is a zero row (the reference writes NaN).  One launch, capturable."""
+    fn = 'colorsB_final'
+    _bf_tensor(fn, points, 'points', torch.int16, 3)
+    level = _bf_level(fn, level)
+    h, w = _bf_depth(fn, depth_map)
+    n = points.size(0)
+    _bf_need(fn, isinstance(image, torch.Tensor) and image.dtype == torch.float32 and tuple(image.shape) == (h, w, 3) and
+             image.is_cuda and image.is_contiguous(), f'image must be a contiguous CUDA float tensor of size ({h}, {w}, 3)')
+    _bf_tensor(fn, probabilities, 'probabilities', torch.float32)
+    _bf_need(fn, probabilities.numel() == n, f'probabilities has {probabilities.numel()} entries for {n} points')
+    _bf_same_device(fn, points, depth_map, image, probabilities)
+    _bf_need(fn, float(sigma) > 0.0, 'sigma must be strictly positive')
+    T = _bf_cam(fn, cam, level)
+    lib, dev = _lib.load(), points.device
+    with _lib.on_device(dev):
+        colors = torch.empty((n, 4), dtype=torch.uint8, device=dev)
+        normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_spc_bf_colors_final(_lib.stream_ptr(dev), n, _lib.ptr(points), ctypes.cast(T, ctypes.c_void_p), float(sigma),
+                                                _lib.ptr(image), _lib.ptr(depth_map), h, w, _lib.ptr(probabilities), _lib.ptr(colors),
+                                                _lib.ptr(normals)), fn)
+    return colors, normals
+
+
+def inclusive_sum(inputs):
+    """reference: recon.cpp ``inclusive_sum``: int32 (n) -> its inclusive sum, int32 (the two-level block scan of the octree build).
+    Two launches, capturable."""
+    fn = 'inclusive_sum'
+    _bf_tensor(fn, inputs, 'inputs', torch.int32)
+    lib, dev, n = _lib.load(), inputs.device, inputs.numel()
+    with _lib.on_device(dev):
+        out = torch.empty_like(inputs)
+        if n > 0:
+            ws = _lib.workspace(lib.kamd_spc_bf_scan_workspace(n), dev)
+            _lib.check(lib.kamd_spc_bf_inclusive_sum(_lib.stream_ptr(dev), n, _lib.ptr(inputs), _lib.ptr(out), _lib.ptr(ws)), fn)
+    return out
+
+
+def _bf_compact(fn, points, insum, subdivide):
+    _bf_tensor(fn, points, 'points', torch.int16, 3)
+    _bf_tensor(fn, insum, 'insum', torch.int32)
+    _bf_same_device(fn, points, insum)
+    n, dev = points.size(0), points.device
+    _bf_need(fn, insum.numel() == n, f'insum has {insum.numel()} entries for {n} points')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        npass = int(insum[-1]) if n > 0 else 0          # the host read
+        _bf_need(fn, 0 <= npass <= n, f'insum ends at {npass} for {n} points: not an inclusive sum of 0 / 1 flags')
+        new_points = torch.zeros((8 * npass if subdivide else npass, 3), dtype=torch.int16, device=dev)
+        nvsum = torch.zeros(npass, dtype=torch.int32 if subdivide else torch.long, device=dev)
+        op = lib.kamd_spc_bf_subdivide if subdivide else lib.kamd_spc_bf_compactify
+        _lib.check(op(_lib.stream_ptr(dev), n, npass, _lib.ptr(points), _lib.ptr(insum), _lib.ptr(new_points), _lib.ptr(nvsum)), fn)
+    return new_points, nvsum
+
+
+def subdivide(points, insum):
+    """reference: recon.cpp ``subdivide``: the kept points (insum steps) -> (their 8 children each (8 * pass, 3) short, nvsum (pass)
+    int32: the index of every kept point).  One host read (pass), one launch."""
+    return _bf_compact('subdivide', points, insum, True)
+
+
+def compactify(points, insum):
+    """reference: recon.cpp ``compactify``: -> (the kept points (pass, 3), nvsum (pass) int64)."""
+    return _bf_compact('compactify', points, insum, False)
+
+
+def process_final_voxels(num_nodes, total_nodes, state, nvsum, occupancies, prev_state, octree, empty):
+    """reference: bf.cpp ``process_final_voxels``: the states of 8 * num_nodes sibling voxels -> the nodes' octree / empty bytes and
+    occupancies, written IN PLACE at ``size - total_nodes`` of the three buffers, and the parents' states into prev_state at nvsum.
+    Returns (octree, empty, occupancies).  One launch, capturable."""
+    fn = 'process_final_voxels'
+    num_nodes, total_nodes = int(num_nodes), int(total_nodes)
+    for t, name, dt in ((state, 'state', torch.int32), (nvsum, 'nvsum', torch.int32), (occupancies, 'occupancies', torch.int32),
+                        (prev_state, 'prev_state', torch.int32), (octree, 'octree', torch.uint8), (empty, 'empty', torch.uint8)):
+        _bf_tensor(fn, t, name, dt)
+    _bf_same_device(fn, state, nvsum, occupancies, prev_state, octree, empty)
+    size = octree.numel()
+    _bf_need(fn, empty.numel() == size and occupancies.numel() == size, 'octree, empty and occupancies must have the same size')
+    _bf_need(fn, 0 <= num_nodes <= total_nodes <= size, f'expected 0 <= num_nodes ({num_nodes}) <= total_nodes ({total_nodes}) <= '
+                                                        f'the buffers\' size ({size})')
+    _bf_need(fn, state.numel() >= 8 * num_nodes and nvsum.numel() >= num_nodes,
+             f'state has {state.numel()} entries and nvsum {nvsum.numel()} for {num_nodes} nodes')
+    lib, dev, at = _lib.load(), octree.device, size - total_nodes
+    with _lib.on_device(dev):
+        _lib.check(lib.kamd_spc_bf_process_final_voxels(
+            _lib.stream_ptr(dev), num_nodes, _lib.ptr(state), _lib.ptr(nvsum), prev_state.numel(), occupancies.data_ptr() + 4 * at,
+            _lib.ptr(prev_state), octree.data_ptr() + at, empty.data_ptr() + at), fn)
+    return octree, empty, occupancies
+
+
+def compactify_nodes(total_nodes, insum, octree, empty):
+    """reference: bf.cpp ``compactify_nodes``: the first total_nodes bytes of octree / empty whose insum steps -> (octree, empty)
+    compacted.  Reads the scan's prefix of total_nodes entries only.  One host read, one launch."""
+    fn = 'compactify_nodes'
+    total_nodes = int(total_nodes)
+    _bf_tensor(fn, insum, 'insum', torch.int32)
+    _bf_tensor(fn, octree, 'octree', torch.uint8)
+    _bf_tensor(fn, empty, 'empty', torch.uint8)
+    _bf_same_device(fn, insum, octree, empty)
+    _bf_need(fn, 0 <= total_nodes <= min(insum.numel(), octree.numel(), empty.numel()),
+             f'total_nodes {total_nodes} exceeds insum ({insum.numel()}), octree ({octree.numel()}) or empty ({empty.numel()})')
+    lib, dev = _lib.load(), octree.device
+    with _lib.on_device(dev):
+        npass = int(insum[total_nodes - 1]) if total_nodes > 0 else 0       # the host read
+        _bf_need(fn, 0 <= npass <= total_nodes, f'insum reaches {npass} after {total_nodes} nodes: not an inclusive sum of 0 / 1 flags')
+        new_octree = torch.zeros(npass, dtype=torch.uint8, device=dev)
+        new_empty = torch.zeros(npass, dtype=torch.uint8, device=dev)
+        _lib.check(lib.kamd_spc_bf_compactify_nodes(_lib.stream_ptr(dev), total_nodes, npass, _lib.ptr(insum), _lib.ptr(octree),
+                                                    _lib.ptr(empty), _lib.ptr(new_octree), _lib.ptr(new_empty)), fn)
+    return new_octree, new_empty
+
+
+def _bf_tree(fn, octree, empty, exsum, k=''):
+    _bf_tensor(fn, octree, f'octree{k}', torch.uint8)
+    _bf_tensor(fn, empty, f'empty{k}', torch.uint8)
+    _bf_tensor(fn, exsum, f'exsum{k}', torch.int32)
+    _bf_need(fn, empty.numel() == octree.numel(), f'empty{k} has {empty.numel()} bytes, octree{k} {octree.numel()}')
+    if exsum.numel() != octree.numel():
+        raise ValueError(f'{fn}: exsum{k} has {exsum.numel()} entries for {octree.numel()} octree bytes; only the current layout '
+                         '(num_bytes entries, inclusive sums) is accepted, not the legacy one with a leading 0 per octree')
+
+
+def merge_empty(points, level, octree0, octree1, empty0, empty1, exsum0, exsum1):
+    """reference: bf.cpp ``merge_empty``: points of ``level`` looked up in two (octree, empty) trees -> (occupancy, state): empty
+    where either tree is empty, unseen where both are unseen, occupied otherwise.  One launch, capturable."""
+    fn = 'merge_empty'
+    _bf_tensor(fn, points, 'points', torch.int16, 3)
+    level = _bf_level(fn, level)
+    _bf_tree(fn, octree0, empty0, exsum0, '0')
+    _bf_tree(fn, octree1, empty1, exsum1, '1')
+    _bf_same_device(fn, points, octree0, octree1, empty0, empty1, exsum0, exsum1)
+    lib, dev, n = _lib.load(), points.device, points.size(0)
+    with _lib.on_device(dev):
+        occ = torch.empty(n, dtype=torch.int32, device=dev)
+        state = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(lib.kamd_spc_bf_merge_empty(_lib.stream_ptr(dev), n, _lib.ptr(points), level, octree0.numel(), octree1.numel(),
+                                               _lib.ptr(octree0), _lib.ptr(octree1), _lib.ptr(empty0), _lib.ptr(empty1),
+                                               _lib.ptr(exsum0), _lib.ptr(exsum1), _lib.ptr(occ), _lib.ptr(state)), fn)
+    return occ, state
+
+
+def bq_merge(points, level, octree0, octree1, empty0, empty1, pyramid0, pyramid1, probs0, probs1, colors0, colors1, normals0,
+             normals1, exsum0, exsum1):
+    """reference: bf.cpp ``bq_merge``: the closed-form fusion p0 p1 / (p0 p1 + (1 - p0)(1 - p1)) of two trees at the points of
+    ``level`` -> (occupancy, state, probabilities, colors, normals); unoccupied rows are zero, normals are all zero (as in the
+    reference).  One launch, capturable."""
+    fn = 'bq_merge'
+    _bf_tensor(fn, points, 'points', torch.int16, 3)
+    level = _bf_level(fn, level)
+    _bf_tree(fn, octree0, empty0, exsum0, '0')
+    _bf_tree(fn, octree1, empty1, exsum1, '1')
+    offs = []
+    for k, (pyr, probs, colors) in enumerate(((pyramid0, probs0, colors0), (pyramid1, probs1, colors1))):
+        _bf_need(fn, isinstance(pyr, torch.Tensor) and not pyr.is_cuda and pyr.dim() == 3 and pyr.size(1) == 2 and
+                 pyr.size(2) >= level + 2, f'pyramid{k} must be a CPU tensor of size (1, 2, max_level + 2) with max_level >= {level}')
+        _bf_tensor(fn, probs, f'probs{k}', torch.float32)
+        _bf_tensor(fn, colors, f'colors{k}', torch.uint8, 4)
+        _bf_need(fn, colors.size(0) == probs.numel(), f'colors{k} has {colors.size(0)} rows, probs{k} {probs.numel()}')
+        offs.append(int(pyr[0, 1, level]))
+    _bf_same_device(fn, points, octree0, octree1, empty0, empty1, exsum0, exsum1, probs0, probs1, colors0, colors1)
+    lib, dev, n = _lib.load(), points.device, points.size(0)
+    with _lib.on_device(dev):
+        occ = torch.empty(n, dtype=torch.int32, device=dev)
+        state = torch.empty(n, dtype=torch.int32, device=dev)
+        probs = torch.empty(n, dtype=torch.float32, device=dev)
+        colors = torch.empty((n, 4), dtype=torch.uint8, device=dev)
+        normals = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_spc_bf_merge(_lib.stream_ptr(dev), n, _lib.ptr(points), level, octree0.numel(), octree1.numel(),
+                                         _lib.ptr(octree0), _lib.ptr(octree1), _lib.ptr(empty0), _lib.ptr(empty1), _lib.ptr(exsum0),
+                                         _lib.ptr(exsum1), offs[0], offs[1], probs0.numel(), probs1.numel(), _lib.ptr(probs0),
+                                         _lib.ptr(probs1), _lib.ptr(colors0), _lib.ptr(colors1), _lib.ptr(occ), _lib.ptr(state),
+                                         _lib.ptr(probs), _lib.ptr(colors)), fn)
+    return occ, state, probs, colors, normals
+
+
+def query_cuda_empty(octree, empty, exsum, query_coords, level):
+    """reference: query.cpp ``query_cuda_empty``: query_coords (Q, 3) half / float / double in [-1, 1] -> int32 (Q): >= 0 the point
+    index, -1 empty space or outside the cube, -2 - depth unseen space (``depth`` levels left below the node where the walk
+    stopped).  Quantised as floor(2^level (q / 2 + 1 / 2)) in double.  One launch, capturable."""
+    fn = 'query_cuda_empty'
+    _bf_tree(fn, octree, empty, exsum)
+    level = _bf_level(fn, level)
+    _bf_need(fn, isinstance(query_coords, torch.Tensor) and query_coords.is_cuda and query_coords.is_contiguous() and
+             query_coords.dim() == 2 and query_coords.size(1) == 3, 'query_coords must be a contiguous CUDA tensor of size (Q, 3)')
+    _bf_same_device(fn, octree, empty, exsum, query_coords)
+    sfx = _lib.dtype_suffix(query_coords.dtype, fn, allowed=('f16', 'f32', 'f64'))
+    lib, dev, Q = _lib.load(), octree.device, query_coords.size(0)
+    with _lib.on_device(dev):
+        if octree.numel() == 0 and level > 0:
+            return torch.full((Q,), -1, dtype=torch.int32, device=dev)
+        out = torch.empty(Q, dtype=torch.int32, device=dev)
+        _lib.check(getattr(lib, f'kamd_spc_bf_query_{sfx}')(_lib.stream_ptr(dev), Q, level, octree.numel(), _lib.ptr(octree),
+                                                           _lib.ptr(empty), _lib.ptr(exsum), _lib.ptr(query_coords), _lib.ptr(out)), fn)
+    return out
+
+
+def bf_cells_cuda(octree, empty, level):
+    """(no reference counterpart) The cells of ``level`` that query_cuda_empty does not answer with -1 -- occupied leaves and every
+    cell of an unseen block -- as (K, 3) short in ascending Morton order: what the reference's densifier gets from querying all
+    8^level cells of a dense grid, with work proportional to K.  A count per node, level by level from the leaves up (an occupied
+    leaf bit counts 1, an unseen bit at depth d counts 8^(level - 1 - d), an inner bit its child's count), one host read of K, and
+    one thread per output cell that walks down from the root skipping whole subtrees by their counts."""
+    fn = 'bf_cells_cuda'
+    _bf_tensor(fn, octree, 'octree', torch.uint8)
+    _bf_tensor(fn, empty, 'empty', torch.uint8)
+    _bf_same_device(fn, octree, empty)
+    _bf_need(fn, empty.numel() == octree.numel(), f'empty has {empty.numel()} bytes, octree {octree.numel()}')
+    level = _bf_level(fn, level)
+    _bf_need(fn, level <= 14, 'the count of an unseen root bit, 8^(level - 1), must fit the walk: level at most 14')
+    lib, dev, nb = _lib.load(), octree.device, octree.numel()
+    with _lib.on_device(dev):
+        if level == 0:
+            return torch.zeros((1, 3), dtype=torch.int16, device=dev)
+        if nb == 0:
+            return torch.zeros((0, 3), dtype=torch.int16, device=dev)
+        _bf_need(fn, nb * 8 < 2 ** 31, f'{nb} bytes: the octree must stay below 2^28 bytes')
+        ws = _lib.workspace(lib.kamd_spc_bf_cells_workspace(nb), dev)
+        host = (ctypes.c_int64 * 2)()
+        sp = _lib.stream_ptr(dev)
+        _lib.check(lib.kamd_spc_bf_cells_count(sp, nb, level, _lib.ptr(octree), _lib.ptr(empty), _lib.ptr(ws),
+                                               ctypes.cast(host, ctypes.c_void_p)), fn)
+        K, used = int(host[0]), int(host[1])            # the one host read
+        _bf_need(fn, used == nb, f'{level} levels of the octree account for {used} bytes, it holds {nb}')
+        _bf_need(fn, 0 <= K <= 8 ** level, f'the counts of the octree give {K} cells, level {level} has {8 ** level}')
+        cells = torch.empty((K, 3), dtype=torch.int16, device=dev)
+        _lib.check(lib.kamd_spc_bf_cells_emit(sp, nb, level, _lib.ptr(octree), _lib.ptr(empty), _lib.ptr(ws), K, _lib.ptr(cells)), fn)
+    return cells
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
@@ -1280,4 +1640,9 @@ spc = _types.SimpleNamespace(points_to_morton_cuda=points_to_morton_cuda, morton
                              interpolate_trilinear_backward_feats_cuda=interpolate_trilinear_backward_feats_cuda,
                              interpolate_trilinear_backward_coords_cuda=interpolate_trilinear_backward_coords_cuda,
                              Conv3d_forward=Conv3d_forward, Conv3d_backward=Conv3d_backward,
-                             ConvTranspose3d_forward=ConvTranspose3d_forward, ConvTranspose3d_backward=ConvTranspose3d_backward)
+                             ConvTranspose3d_forward=ConvTranspose3d_forward, ConvTranspose3d_backward=ConvTranspose3d_backward,
+                             build_mip2d=build_mip2d, oracleB=oracleB, oracleB_final=oracleB_final, colorsB_final=colorsB_final,
+                             inclusive_sum=inclusive_sum, subdivide=subdivide, compactify=compactify,
+                             process_final_voxels=process_final_voxels, compactify_nodes=compactify_nodes,
+                             merge_empty=merge_empty, bq_merge=bq_merge, query_cuda_empty=query_cuda_empty,
+                             bf_cells_cuda=bf_cells_cuda)

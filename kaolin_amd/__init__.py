@@ -10,6 +10,8 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
                                 subdivide_trianglemesh (Loop subdivision with a per-vertex alpha, HIP pipeline)
     kaolin_amd.ops.spc          the SPC core: scan_octrees, generate_points, unbatched_query, to_dense, unbatched_points_to_octree (HIP),
                                 conv3d / conv_transpose3d and their layers (HIP neighbour map + MFMA gather-GEMM)
+    kaolin_amd.ops.spc.bf_recon bf_recon, fuseBF, the empty-aware unbatched_query (HIP operators of csrc/spc_bf.hip)
+    kaolin_amd.ops.gaussians    sample_points_in_volume: fills a shell of Gaussian splats (also as kaolin_amd.ops.gaussian)
     kaolin_amd.rep              Spc, the structured point cloud data class
     kaolin_amd.ops.voxelgrid    fill (HIP flood fill over bit grids), downsample, extract_surface, extract_odms, project_odms
     kaolin_amd.metrics.voxelgrid  iou

@@ -119,6 +119,26 @@ SIGNATURES.update({
     'kamd_gs_to_spc_finish': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'kamd_integrate_gs': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
 })
+SIGNATURES.update({
+    'kamd_spc_bf_mip_size': (_i64, [_i, _i, _i]),
+    'kamd_spc_bf_build_mip2d': (_i, [_vp, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+    'kamd_spc_bf_oracle': (_i, [_vp, _i64, _vp, _i, _vp, _f, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'kamd_spc_bf_oracle_final': (_i, [_vp, _i64, _vp, _i, _vp, _f, _vp, _i, _i, _vp, _vp, _vp]),
+    'kamd_spc_bf_colors_final': (_i, [_vp, _i64, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'kamd_spc_bf_scan_workspace': (_sz, [_i64]),
+    'kamd_spc_bf_inclusive_sum': (_i, [_vp, _i64, _vp, _vp, _vp]),
+    'kamd_spc_bf_subdivide': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'kamd_spc_bf_compactify': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'kamd_spc_bf_process_final_voxels': (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'kamd_spc_bf_compactify_nodes': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'kamd_spc_bf_merge_empty': (_i, [_vp, _i64, _vp, _i, _i64, _i64] + [_vp] * 8),
+    'kamd_spc_bf_merge': (_i, [_vp, _i64, _vp, _i, _i64, _i64] + [_vp] * 6 + [_i64] * 4 + [_vp] * 8),
+    'kamd_spc_bf_cells_workspace': (_sz, [_i64]),
+    'kamd_spc_bf_cells_count': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    'kamd_spc_bf_cells_emit': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _vp]),
+})
+for _t in ('f16', 'f32', 'f64'):
+    SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_spc_conv_gather_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_spc_conv_wgrad_{_t}'] = (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp])
