@@ -1020,9 +1020,12 @@ int kamd_tetmesh_amips_backward_f64(void* stream, int64_t B, int64_t T, const do
 /* compares each data-derived index with them: an index out of range is a miss */
 /* (query) or a skipped write (the others), never an access.                   */
 /*   points_to_morton / morton_to_points / points_to_corners: one launch each. */
-/*   octree_build: codes (any order, duplicates allowed unless `sorted`) are   */
+/*   octree_build: codes (any order, duplicates allowed) are                   */
 /*     masked to 3*level bits, sorted (keys-only radix sort, 8 bits a pass),   */
 /*     made unique, and every level is built bottom-up in the workspace        */
+/*     `sorted` promises ascending codes and skips the sort only: the unique   */
+/*     pass still runs, so equal neighbours are allowed (pointcloud.hip passes */
+/*     its sorted keys with their duplicates and reads U from host_sizes[0])   */
 /*     (kamd_spc_octree_workspace(n, level) bytes).  host_sizes (HOST memory,  */
 /*     1 + level int64: unique codes, then nodes per level root first) is the  */
 /*     one host read: the call synchronises the stream.  octree_gather then    */
@@ -1302,6 +1305,50 @@ int kamd_spc_bf_cells_count(void* stream, int64_t num_bytes, int level, const ui
                             int64_t* host2);
 int kamd_spc_bf_cells_emit(void* stream, int64_t num_bytes, int level, const uint8_t* octree, const uint8_t* empty, const void* workspace,
                            int64_t K, int16_t* cells);
+
+/* ------------------------------------------------------------------------- */
+/* ops.conversions.pointcloud (csrc/pointcloud.hip; the reference's versions   */
+/* are pure PyTorch, these entry points exist only on our side).               */
+/* unbatched_pointcloud_to_spc, in this order:                                 */
+/*   spc_build_*: n points (f32 / f64 with element strides, quantised as       */
+/*     ops.spc.quantize_points does; i16: (n, 3) contiguous, quantised by the  */
+/*     caller) -> (Morton key, index) pairs, the stable pair sort on 3 * level */
+/*     bits, run heads, scan, run starts, then kamd_spc_octree_build on the    */
+/*     sorted keys.  host_sizes (1 + level): unique cells U, then the nodes of */
+/*     every level -- the ONE host read; the call synchronises the stream.     */
+/*     workspace: kamd_pointcloud_spc_workspace(n, level) bytes, kept for the  */
+/*     next two calls.                                                         */
+/*   spc_octree: the sum(host_sizes[1:]) bytes of the octree.                  */
+/*   spc_mean: features (n, D) with element strides, dtype 0..8 = bool, u8,    */
+/*     i8, i16, i32, i64, f16, f32, f64 -> out (U, D) contiguous, row r = the  */
+/*     mean of the r-th cell in Morton order: double sums in a fixed order     */
+/*     (pointcloud.hip states it), one division, rint for the integer types,   */
+/*     one cast.  No atomics.  mean_workspace:                                 */
+/*     kamd_pointcloud_spc_mean_workspace(n, D) bytes.  Two launches.          */
+/* voxelgrids_*: points (B, P, 3), origin (B, 3), scale (B) contiguous; mult = */
+/*   R - 1 rounded to the dtype.  sparse == 0: out = (B, R, R, R) grid of the  */
+/*   dtype, zeroed here, 1 where round_half_even(((p - origin) / scale) mult)  */
+/*   lies in [0, R - 1]^3, every operation rounded in the dtype.  sparse != 0: */
+/*   out = (B, ceil(R^3 / 32)) 32-bit words, zeroed here, bit (lin & 31) of    */
+/*   word lin / 32 for the voxel lin = (x R + y) R + z.  One launch.           */
+/* ------------------------------------------------------------------------- */
+size_t kamd_pointcloud_spc_workspace(int64_t n, int level);
+int kamd_pointcloud_spc_build_f32(void* stream, int64_t n, int level, const float* points, int64_t stride_n, int64_t stride_c,
+                                  void* workspace, size_t workspace_bytes, int64_t* host_sizes);
+int kamd_pointcloud_spc_build_f64(void* stream, int64_t n, int level, const double* points, int64_t stride_n, int64_t stride_c,
+                                  void* workspace, size_t workspace_bytes, int64_t* host_sizes);
+int kamd_pointcloud_spc_build_i16(void* stream, int64_t n, int level, const int16_t* points, void* workspace, size_t workspace_bytes,
+                                  int64_t* host_sizes);
+int kamd_pointcloud_spc_octree(void* stream, int64_t n, int level, const void* workspace, int64_t octree_bytes, uint8_t* octree);
+size_t kamd_pointcloud_spc_mean_workspace(int64_t n, int64_t D);
+int kamd_pointcloud_spc_mean(void* stream, int dtype, int64_t n, int level, int64_t U, int64_t D, const void* features,
+                             int64_t stride_n, int64_t stride_d, const void* workspace, void* mean_workspace, void* out);
+int kamd_pointcloud_voxelgrids_f16(void* stream, int64_t B, int64_t P, int R, double mult, const void* points, const void* origin,
+                                   const void* scale, int sparse, void* out);
+int kamd_pointcloud_voxelgrids_f32(void* stream, int64_t B, int64_t P, int R, double mult, const float* points,
+                                   const float* origin, const float* scale, int sparse, void* out);
+int kamd_pointcloud_voxelgrids_f64(void* stream, int64_t B, int64_t P, int R, double mult, const double* points,
+                                   const double* origin, const double* scale, int sparse, void* out);
 
 /* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */

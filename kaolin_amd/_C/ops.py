@@ -1616,6 +1616,98 @@ def bf_cells_cuda(octree, empty, level):
     return cells
 
 
+# ---- kaolin._C.ops.conversions: point clouds on csrc/pointcloud.hip (no reference counterpart: pure PyTorch there) -----------------
+_PC_DTYPES = {torch.bool: 0, torch.uint8: 1, torch.int8: 2, torch.int16: 3, torch.int32: 4, torch.int64: 5, torch.float16: 6,
+              torch.float32: 7, torch.float64: 8}
+
+
+def pointcloud_to_spc_cuda(pointcloud, level, features=None):
+    """pointcloud (N, 3) float / double of any strides, or short (quantised by the caller, contiguous); features (N, D) of any strides,
+    bool / uint8 / int8 / int16 / int32 / int64 / half / float / double, or None -> (octree (num_bytes) uint8, features (U, D) or
+    None): the octree of the occupied cells of ``level`` and the mean feature of every cell, in Morton order.
+
+    Launches: 1 (keys) + 4 per 8 key bits (the pair sort) + 4 (run heads, scan, run starts) + 5 + 4 * level (the octree build) + 1
+    (gather) + 2 (the mean).  ONE host read (unique cells and level sizes together); the call synchronises the current stream and
+    cannot be captured in a graph."""
+    fn = 'pointcloud_to_spc_cuda'
+    torch_check(pointcloud.is_cuda, f'{fn}: pointcloud must be a CUDA tensor')
+    torch_check(pointcloud.dim() == 2 and pointcloud.size(1) == 3, f'{fn}: pointcloud must be Nx3')
+    torch_check(pointcloud.dtype in (torch.float32, torch.float64, torch.int16), f'{fn}: pointcloud must be float, double or short')
+    level, n, dev = int(level), pointcloud.size(0), pointcloud.device
+    torch_check(1 <= level <= SPC_MAX_LEVEL, f'{fn}: level must be in [1, {SPC_MAX_LEVEL}]')
+    torch_check(n > 0, f'{fn}: no points')
+    if features is not None:
+        torch_check(features.is_cuda and features.device == dev, f'{fn}: features must be on the pointcloud\'s device')
+        torch_check(features.dim() == 2 and features.size(0) == n and features.size(1) >= 1, f'{fn}: features must be NxD, D >= 1')
+        torch_check(features.dtype in _PC_DTYPES, f'{fn}: features of {features.dtype} are not supported')
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_pointcloud_spc_workspace(n, level)
+        ws = _lib.workspace(nbytes, dev)
+        sizes = (ctypes.c_int64 * (1 + level))()
+        host = ctypes.cast(sizes, ctypes.c_void_p)
+        if pointcloud.dtype == torch.int16:
+            torch_check(pointcloud.is_contiguous(), f'{fn}: quantised points must be contiguous')
+            st = lib.kamd_pointcloud_spc_build_i16(sp, n, level, _lib.ptr(pointcloud), _lib.ptr(ws), nbytes, host)
+        else:
+            sfx = 'f32' if pointcloud.dtype == torch.float32 else 'f64'
+            st = getattr(lib, f'kamd_pointcloud_spc_build_{sfx}')(sp, n, level, _lib.ptr(pointcloud), pointcloud.stride(0),
+                                                                   pointcloud.stride(1), _lib.ptr(ws), nbytes, host)
+        _lib.check(st, fn)
+        U, octree_bytes = int(sizes[0]), sum(sizes[1:])        # data-dependent sizes: the one host read
+        if not (1 <= U <= n and 1 <= octree_bytes <= level * n):
+            raise RuntimeError(f'{fn}: the build reports {U} cells and {octree_bytes} octree bytes for {n} points')
+        octree = torch.empty(octree_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.kamd_pointcloud_spc_octree(sp, n, level, _lib.ptr(ws), octree_bytes, _lib.ptr(octree)), fn)
+        feats = None
+        if features is not None:
+            f = features.detach()
+            D = f.size(1)
+            feats = torch.empty((U, D), dtype=f.dtype, device=dev)
+            mws = _lib.workspace(lib.kamd_pointcloud_spc_mean_workspace(n, D), dev)
+            _lib.check(lib.kamd_pointcloud_spc_mean(sp, _PC_DTYPES[f.dtype], n, level, U, D, _lib.ptr(f), f.stride(0), f.stride(1),
+                                                    _lib.ptr(ws), _lib.ptr(mws), _lib.ptr(feats)), fn)
+    return octree, feats
+
+
+def pointclouds_to_voxelgrids_cuda(pointclouds, resolution, origin, scale, return_sparse=False):
+    """pointclouds (B, P, 3) half / float / double, origin (B, 3), scale (B) of the same dtype -> dense (B, R, R, R) grid of 0/1 in
+    that dtype (a zero fill and one launch, no host read), or with ``return_sparse`` the coalesced sparse COO tensor of the same
+    voxels, compacted from a BIT grid (R^3 / 8 bytes per item; R^3 scalars are never allocated) as trianglemeshes_to_voxelgrids_cuda
+    does: two ``nonzero`` calls, i.e. two host reads."""
+    fn = 'pointclouds_to_voxelgrids_cuda'
+    torch_check(pointclouds.is_cuda, f'{fn}: pointclouds must be a CUDA tensor')
+    torch_check(pointclouds.dim() == 3 and pointclouds.size(2) == 3, f'{fn}: pointclouds must be of size {{batch_size, num_points, 3}}')
+    sfx = _lib.dtype_suffix(pointclouds.dtype, fn, allowed=('f16', 'f32', 'f64'))
+    p = pointclouds.detach().contiguous()
+    B, P, R, dev, dtype = p.size(0), p.size(1), int(resolution), p.device, p.dtype
+    torch_check(1 <= R <= 2048, f'{fn}: resolution must be in [1, 2048]')
+    for name, t, shape in (('origin', origin, (B, 3)), ('scale', scale, (B,))):
+        torch_check(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape,
+                    f'{fn}: {name} must be a {dtype} tensor of size {shape} on the pointclouds\' device')
+    origin, scale = origin.detach().contiguous(), scale.detach().contiguous()
+    mult = float((torch.ones(1, dtype=dtype) * (R - 1)).item())            # R - 1 as the dtype holds it (CPU arithmetic: no read)
+    lib = _lib.load()
+    call = getattr(lib, f'kamd_pointcloud_voxelgrids_{sfx}')
+    with _lib.on_device(dev):
+        if not return_sparse:
+            grid = torch.empty((B, R, R, R), dtype=dtype, device=dev)
+            _lib.check(call(_lib.stream_ptr(dev), B, P, R, mult, _lib.ptr(p), _lib.ptr(origin), _lib.ptr(scale), 0, _lib.ptr(grid)), fn)
+            return grid
+        words = (R ** 3 + 31) // 32
+        bits = torch.empty((B, words), dtype=torch.int32, device=dev)
+        _lib.check(call(_lib.stream_ptr(dev), B, P, R, mult, _lib.ptr(p), _lib.ptr(origin), _lib.ptr(scale), 1, _lib.ptr(bits)), fn)
+        # compaction, sized by the occupied words (see trianglemeshes_to_voxelgrids_cuda): ascending linear indices per item
+        nzw = torch.nonzero(bits)
+        w = bits[nzw[:, 0], nzw[:, 1]]
+        on = ((w.unsqueeze(1) >> torch.arange(32, device=dev, dtype=torch.int32)) & 1).bool()
+        sel = torch.nonzero(on)
+        lin = nzw[sel[:, 0], 1] * 32 + sel[:, 1]
+        idx = torch.stack([nzw[sel[:, 0], 0], lin // (R * R), (lin // R) % R, lin % R])
+        return torch.sparse_coo_tensor(idx, torch.ones(idx.shape[1], dtype=dtype, device=dev), (B, R, R, R), is_coalesced=True)
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
@@ -1628,7 +1720,9 @@ mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_in
 conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
                                      marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda,
                                      voxelgrids_to_cubic_meshes_cuda=voxelgrids_to_cubic_meshes_cuda,
-                                     gs_to_spc_cuda=gs_to_spc_cuda, integrate_gs_cuda=integrate_gs_cuda)
+                                     gs_to_spc_cuda=gs_to_spc_cuda, integrate_gs_cuda=integrate_gs_cuda,
+                                     pointcloud_to_spc_cuda=pointcloud_to_spc_cuda,
+                                     pointclouds_to_voxelgrids_cuda=pointclouds_to_voxelgrids_cuda)
 spc = _types.SimpleNamespace(points_to_morton_cuda=points_to_morton_cuda, morton_to_points_cuda=morton_to_points_cuda,
                              points_to_corners_cuda=points_to_corners_cuda, points_to_octree=points_to_octree,
                              morton_to_octree=morton_to_octree, scan_octrees_cuda=scan_octrees_cuda,

@@ -137,6 +137,17 @@ SIGNATURES.update({
     'kamd_spc_bf_cells_count': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
     'kamd_spc_bf_cells_emit': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _vp]),
 })
+SIGNATURES.update({
+    'kamd_pointcloud_spc_workspace': (_sz, [_i64, _i]),
+    'kamd_pointcloud_spc_build_f32': (_i, [_vp, _i64, _i, _vp, _i64, _i64, _vp, _sz, _vp]),
+    'kamd_pointcloud_spc_build_f64': (_i, [_vp, _i64, _i, _vp, _i64, _i64, _vp, _sz, _vp]),
+    'kamd_pointcloud_spc_build_i16': (_i, [_vp, _i64, _i, _vp, _vp, _sz, _vp]),
+    'kamd_pointcloud_spc_octree': (_i, [_vp, _i64, _i, _vp, _i64, _vp]),
+    'kamd_pointcloud_spc_mean_workspace': (_sz, [_i64, _i64]),
+    'kamd_pointcloud_spc_mean': (_i, [_vp, _i, _i64, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+})
+for _t in ('f16', 'f32', 'f64'):
+    SIGNATURES[f'kamd_pointcloud_voxelgrids_{_t}'] = (_i, [_vp, _i64, _i64, _i, _dbl, _vp, _vp, _vp, _i, _vp])
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):

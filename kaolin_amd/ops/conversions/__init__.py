@@ -6,3 +6,5 @@ from .voxelgrid import voxelgrids_to_cubic_meshes  # noqa: F401
 from . import voxelgrid  # noqa: F401
 from .gaussians import gs_to_voxelgrid  # noqa: F401
 from . import gaussians  # noqa: F401
+from .pointcloud import pointclouds_to_voxelgrids, unbatched_pointcloud_to_spc  # noqa: F401
+from . import pointcloud  # noqa: F401

@@ -1,0 +1,319 @@
+"""kaolin.ops.conversions.pointcloud on CPU tensors (the torch formulations) against the reference-made goldens
+(tests/golden/pointcloud_voxelgrids.npz), the reference's recorded examples (tests/golden/pointcloud_examples.json) and the oracle of
+tests/pointcloud_bruteforce.py.  The helpers take a device: tests/test_pointcloud_gpu.py runs them on CUDA tensors."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import pointcloud_bruteforce as bf
+from conftest import GOLDEN_DIR
+
+VOXEL_DTYPES = {'f32': torch.float32, 'f64': torch.float64, 'f16': torch.float16}
+INT_DTYPES = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+FLOAT_DTYPES = (torch.float16, torch.float32, torch.float64)
+
+
+def conv():
+    import kaolin_amd
+    return kaolin_amd.ops.conversions
+
+
+def spc_ops():
+    import kaolin_amd
+    return kaolin_amd.ops.spc
+
+
+# ---- voxel grids: the goldens ----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def goldens():
+    with np.load(os.path.join(GOLDEN_DIR, 'pointcloud_voxelgrids.npz')) as z:
+        return {k: z[k] for k in z.files}
+
+
+def golden_cases(tag):
+    return [str(c) for c in goldens()['cases'] if str(c).endswith('_' + tag)]
+
+
+def golden_case(case):
+    """(points, R, origin or None, scale or None, dense (B, R, R, R) bool, indices (4, nnz) int64) of a golden case, CPU tensors"""
+    g = goldens()
+    pts = torch.from_numpy(g[f'{case}_in'])
+    R = int(g[f'{case}_R'])
+    origin = torch.from_numpy(g[f'{case}_origin']) if f'{case}_origin' in g else None
+    scale = torch.from_numpy(g[f'{case}_scale']) if f'{case}_scale' in g else None
+    B = pts.shape[0]
+    dense = torch.from_numpy(np.unpackbits(g[f'{case}_bits'])[:B * R ** 3].astype(bool).reshape(B, R, R, R))
+    return pts, R, origin, scale, dense, torch.from_numpy(g[f'{case}_idx'].astype(np.int64))
+
+
+def check_voxel_case(case, device):
+    pts, R, origin, scale, dense, idx = golden_case(case)
+    to = lambda x: None if x is None else x.to(device)      # noqa: E731
+    got = conv().pointclouds_to_voxelgrids(to(pts), R, origin=to(origin), scale=to(scale))
+    assert got.dtype == pts.dtype and got.device.type == device and got.shape == dense.shape, case
+    assert torch.equal(got.cpu(), dense.to(pts.dtype)), case
+    sp = conv().pointclouds_to_voxelgrids(to(pts), R, origin=to(origin), scale=to(scale), return_sparse=True)
+    assert sp.is_sparse and sp.shape == dense.shape and sp.dtype == pts.dtype, case
+    assert torch.equal(sp.to_dense().cpu(), dense.to(pts.dtype)), case
+    sp = sp.coalesce()
+    assert sp.indices().dtype == torch.int64 and torch.equal(sp.indices().cpu(), idx), case
+    assert torch.equal(sp.values().cpu(), torch.ones(idx.shape[1], dtype=pts.dtype)), case
+    return got
+
+
+# ---- SPC: seeded inputs and the oracle -----------------------------------------------------------------------------------------------
+def cloud(name):
+    """(N, 3) float64 in [-1, 1] (exactly representable in float32; half rounds them)"""
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    if name == 'one':
+        return torch.tensor([[0.25, -0.5, 0.75]], dtype=torch.float64)
+    if name == 'two_same':
+        return torch.tensor([[0.3, 0.3, -0.6]] * 2, dtype=torch.float32).double()
+    if name.startswith('one_cell_'):            # all inside one cell of level 15: [0.5, 0.5 + 2^-14)
+        n = int(name.split('_')[-1])
+        return (0.5 + torch.rand((n, 3), generator=g) * 2.0 ** -15).float().double()
+    if name == 'distinct_257':                  # 257 different cells of level 8 (and of every deeper level)
+        lin = torch.randperm(2 ** 24, generator=g)[:257]
+        cell = torch.stack([lin >> 16, (lin >> 8) & 255, lin & 255], dim=1).double()
+        return (cell + 0.5) / 128.0 - 1.0
+    if name == 'random_2049':
+        return (torch.rand((2049, 3), generator=g) * 2 - 1).float().double()
+    if name == 'special':                       # on and beyond the borders, -0.0, the centre planes, infinities
+        vals = torch.tensor([-1.0, 1.0, -1.5, 1.5, -0.0, 0.0, -1e30, 1e30, float('inf'), float('-inf'), 0.999, -0.999, 2.0 ** -20,
+                             -2.0 ** -20], dtype=torch.float64)
+        pick = torch.randint(0, vals.numel(), (120, 3), generator=g)
+        return vals[pick]
+    raise KeyError(name)
+
+
+def features(n, D, dtype, name):
+    g = torch.Generator().manual_seed(1000 + D + sum(map(ord, name)))
+    if dtype == torch.bool:
+        return torch.rand((n, D), generator=g) < 0.5
+    if dtype == torch.uint8:
+        return torch.randint(0, 201, (n, D), generator=g).to(dtype)
+    if not dtype.is_floating_point:
+        return torch.randint(-100, 101, (n, D), generator=g).to(dtype)     # small: every double sum is exact
+    return (torch.randn((n, D), generator=g, dtype=torch.float64) * 3).to(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def spc_case(name, level, point_dtype, D, feature_dtype):
+    """(points, features or None, oracle): computed once, shared by the tests, never modified"""
+    pts = cloud(name).to(point_dtype)
+    feats = None if D == 0 else features(pts.shape[0], D, feature_dtype, name)
+    return pts, feats, bf.Oracle(pts.numpy(), level, None if feats is None else feats.numpy())
+
+
+def check_spc(name, level, device, point_dtype=torch.float32, D=3, feature_dtype=torch.float32, strided=False):
+    """The octree against the oracle and against unbatched_points_to_octree(quantize_points(...)); integer features bit-equal to
+    the oracle, float features within its derived bound.  -> (spc, share of the bound used or None)"""
+    pts, feats, orc = spc_case(name, level, point_dtype, D, feature_dtype)
+    p, f = pts.to(device), None if feats is None else feats.to(device)
+    if strided:                                 # column slices of wider tensors
+        wide = torch.zeros((p.shape[0], 5), dtype=p.dtype, device=device)
+        wide[:, 1:4] = p
+        p = wide[:, 1:4]
+        assert not p.is_contiguous()
+        if f is not None:
+            wf = torch.zeros((f.shape[0], 2 * f.shape[1] + 1), dtype=f.dtype, device=device)
+            wf[:, 1::2] = f
+            f = wf[:, 1::2]
+            assert not f.is_contiguous() or f.shape[0] == 1
+    spc = conv().unbatched_pointcloud_to_spc(p, level, f)
+    S = spc_ops()
+    assert spc.octrees.dtype == torch.uint8 and spc.octrees.device.type == device
+    assert torch.equal(spc.octrees.cpu(), torch.from_numpy(orc.octree))
+    assert torch.equal(spc.octrees, S.unbatched_points_to_octree(S.quantize_points(p, level), level))
+    assert spc.lengths.dtype == torch.int32 and not spc.lengths.is_cuda and spc.lengths.tolist() == [len(orc.octree)]
+    if feats is None:
+        assert spc.features is None
+        return spc, None
+    got = spc.features
+    assert got.dtype == feats.dtype and got.device.type == device and tuple(got.shape) == (len(orc.codes), D)
+    assert not got.requires_grad
+    if not feats.dtype.is_floating_point:
+        want = torch.from_numpy(orc.integer_features(feats.numpy().dtype))
+        assert torch.equal(got.cpu(), want)
+        return spc, None
+    share = orc.worst_share(got.cpu().numpy())
+    print(f'pointcloud_to_spc {device} {name} level {level} D {D} {feats.dtype}: worst share of the bound {share:.4f}')
+    assert share <= 1.0
+    return spc, share
+
+
+# ---- tests -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('tag', sorted(VOXEL_DTYPES))
+def test_voxelgrids_goldens(tag):
+    cases = golden_cases(tag)
+    assert len(cases) == 33
+    for case in cases:
+        check_voxel_case(case, 'cpu')
+
+
+@pytest.mark.parametrize('tag', sorted(VOXEL_DTYPES))
+def test_voxelgrids_oracle(tag):
+    """the numpy restatement of the contract gives the reference's grids too (ties and the seeded case: where the dtypes differ)"""
+    for name in ('ties_r3', 'ties_r5', 'ties_r7', 'seeded_2x50', 'outside', 'coincide'):
+        pts, R, origin, scale, dense, _ = golden_case(f'{name}_{tag}')
+        if origin is None:
+            origin = pts.min(dim=1)[0]
+            scale = (pts.max(dim=1)[0] - origin).max(dim=1)[0]
+        assert np.array_equal(bf.voxelgrids(pts.numpy(), R, origin.numpy(), scale.numpy()), dense.numpy()), name
+
+
+def test_voxelgrids_dtypes_differ():
+    filled = {tag: int(golden_case(f'seeded_2x50_{tag}')[4].sum()) for tag in VOXEL_DTYPES}
+    assert len(set(filled.values())) > 1, filled
+
+
+def test_voxelgrids_docstring_example():
+    pts = torch.tensor([[[0, 0, 0], [1, 1, 1], [2, 2, 2]]], dtype=torch.float)
+    want = torch.zeros((1, 3, 3, 3))
+    want[0, 0, 0, 0] = want[0, 1, 1, 1] = want[0, 2, 2, 2] = 1
+    assert torch.equal(conv().pointclouds_to_voxelgrids(pts, 3), want)
+
+
+def check_voxelgrids_errors(device):
+    f = conv().pointclouds_to_voxelgrids
+    pts = torch.rand((2, 5, 3), device=device)
+    with pytest.raises(TypeError, match=r"Expected resolution to be int but got <class 'float'>\."):
+        f(pts, 3.0)
+    for bad in (pts[0], pts[..., :2], pts.long()):
+        with pytest.raises(ValueError):
+            f(bad, 3)
+    with pytest.raises(ValueError):
+        f(pts, 0)
+    with pytest.raises(ValueError):
+        f(pts, 3, origin=torch.zeros((2, 2), device=device))
+    with pytest.raises(ValueError):
+        f(pts, 3, scale=torch.ones((2, 1), device=device))
+    with pytest.raises(ValueError):
+        f(pts, 3, origin=torch.zeros((2, 3), device=device, dtype=torch.float64))
+    with pytest.raises(ValueError):
+        f(pts[:, :0], 3)
+    # a NaN or an infinite coordinate marks nothing
+    odd = torch.tensor([[[0.25, 0.5, float('nan')], [float('inf'), 0.5, 0.5], [0.5, float('-inf'), 0.5], [0.5, 0.5, 0.5]]], device=device)
+    got = f(odd, 3, origin=torch.zeros((1, 3), device=device), scale=torch.ones(1, device=device))
+    assert int(got.sum()) == 1 and got[0, 1, 1, 1] == 1
+
+
+def test_voxelgrids_errors():
+    check_voxelgrids_errors('cpu')
+
+
+def examples():
+    with open(os.path.join(GOLDEN_DIR, 'pointcloud_examples.json')) as fh:
+        return json.load(fh)
+
+
+def check_reference_examples(device):
+    ex = examples()
+    f = conv().unbatched_pointcloud_to_spc
+    pc = torch.tensor(ex['pointcloud'], device=device)
+    for level, cut in zip(ex['levels'], ex['level_cutoff']):
+        octree = torch.tensor(ex['full_octree'][:cut], dtype=torch.uint8)
+        for dtype in FLOAT_DTYPES:
+            spc = f(pc.to(dtype), level)
+            assert torch.equal(spc.octrees.cpu(), octree) and spc.features is None
+            assert spc.batch_size == 1 and spc.max_level == level
+        which = 'level1' if level == 1 else 'deeper'
+        assert torch.equal(f(pc, level, torch.tensor(ex['bool_features'], device=device).bool()).features.cpu(),
+                           torch.tensor(ex[f'expected_bool_{which}']).bool())
+        for dtype in INT_DTYPES[1:]:
+            got = f(pc, level, torch.tensor(ex['int_features'], device=device).to(dtype)).features
+            assert torch.equal(got.cpu(), torch.tensor(ex[f'expected_int_{which}']).to(dtype))
+        want = torch.tensor(ex['expected_fp_level1_thirds'], dtype=torch.float64) / 3 if level == 1 else \
+            torch.tensor(ex['expected_fp_deeper'], dtype=torch.float64)
+        for dtype in FLOAT_DTYPES:
+            got = f(pc, level, torch.tensor(ex['fp_features'], device=device).to(dtype)).features
+            assert got.dtype == dtype and torch.allclose(got.cpu(), want.to(dtype))
+    q = ex['consistent_query']
+    pos = torch.tensor(q['points'], device=device)
+    spc = f(pos, q['level'])
+    idx = spc_ops().unbatched_query(spc.octrees, spc.exsum, pos, q['level'])
+    assert idx.tolist() == q['query_idx']
+
+
+def test_reference_examples():
+    check_reference_examples('cpu')
+
+
+def check_spc_fields(device):
+    spc, _ = check_spc('random_2049', 3, device)
+    import kaolin_amd
+    assert isinstance(spc, kaolin_amd.rep.Spc) and spc.batch_size == 1
+    pyr = spc.pyramids
+    assert tuple(pyr.shape) == (1, 2, 5) and int(pyr[0, 0, 3]) == spc.features.shape[0]
+    ph = spc.point_hierarchies
+    assert ph.shape[0] == int(pyr[0, 1, 4]) and ph.dtype == torch.int16
+    # the rows of the features are the points of the last level, in their order
+    pts, _, orc = spc_case('random_2049', 3, torch.float32, 3, torch.float32)
+    last = ph[int(pyr[0, 1, 3]):].cpu().long()
+    assert [bf.morton(x, y, z, 3) for x, y, z in last.tolist()] == orc.codes
+
+
+def test_spc_fields():
+    check_spc_fields('cpu')
+
+
+@pytest.mark.parametrize('name, level', [('one', 8), ('two_same', 8), ('one_cell_300', 15), ('distinct_257', 8), ('random_2049', 1),
+                                         ('random_2049', 8), ('random_2049', 15), ('special', 4)])
+def test_spc_sizes_levels(name, level):
+    check_spc(name, level, 'cpu')
+
+
+@pytest.mark.parametrize('dtype', INT_DTYPES + FLOAT_DTYPES, ids=str)
+def test_spc_feature_dtypes(dtype):
+    check_spc('random_2049', 2, 'cpu', D=3, feature_dtype=dtype, strided=True)
+
+
+@pytest.mark.parametrize('dtype, level', [(torch.float64, 15), (torch.float16, 11), (torch.float16, 3)], ids=str)
+def test_spc_point_dtypes(dtype, level):
+    check_spc('random_2049', level, 'cpu', point_dtype=dtype, D=0)
+    check_spc('special', level, 'cpu', point_dtype=dtype, D=0)
+
+
+def test_spc_nan_quantises_to_zero():
+    pts = torch.tensor([[float('nan'), 0.5, 0.5], [0.5, float('nan'), float('nan')]])
+    spc = conv().unbatched_pointcloud_to_spc(pts, 2)
+    assert torch.equal(spc.octrees, torch.from_numpy(bf.Oracle(pts.numpy(), 2).octree))
+    assert spc.point_hierarchies[-2:].tolist() == [[0, 3, 3], [3, 0, 0]]
+
+
+def check_spc_errors(device):
+    f = conv().unbatched_pointcloud_to_spc
+    pts = torch.rand((6, 3), device=device) * 2 - 1
+    feats = torch.rand((6, 2), device=device)
+    for bad in (pts[0], pts[:, :2], pts.long(), pts[:0]):
+        with pytest.raises(ValueError):
+            f(bad, 3)
+    for level in (0, 16, -1, 2.0, True):
+        with pytest.raises(ValueError):
+            f(pts, level)
+    with pytest.raises(ValueError, match='half'):
+        f(pts.half(), 12)
+    for bad in (feats[:5], feats[:, :0], feats[:, 0], feats.to(torch.complex64), feats.bfloat16()):
+        with pytest.raises(ValueError):
+            f(pts, 3, bad)
+    if device != 'cpu':
+        with pytest.raises(ValueError):
+            f(pts, 3, feats.cpu())
+    assert f(pts, 3, feats.requires_grad_()).features.requires_grad is False
+
+
+def test_spc_errors():
+    check_spc_errors('cpu')
+
+
+def test_exports():
+    import kaolin_amd
+    c = kaolin_amd.ops.conversions
+    assert c.pointcloud.pointclouds_to_voxelgrids is c.pointclouds_to_voxelgrids
+    assert c.pointcloud.unbatched_pointcloud_to_spc is c.unbatched_pointcloud_to_spc
+    assert callable(kaolin_amd._C.ops.conversions.pointcloud_to_spc_cuda)
+    assert callable(kaolin_amd._C.ops.conversions.pointclouds_to_voxelgrids_cuda)
