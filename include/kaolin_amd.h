@@ -606,6 +606,10 @@ int kamd_deftet_sparse_render_backward_f64(void* stream, int B, int F, int P, in
 /*     level)): counts + offsets (n + 1, offsets[n] = total, read by the host); */
 /*     stage_emit writes the `total` surviving (code, triangle) pairs at        */
 /*     level_to; repeat from level_to with tested = 1 until level_to == level.  */
+/*     Both return hipErrorInvalidValue, before any launch, unless              */
+/*     0 <= level_from <= level_to <= 15 and                                    */
+/*     level_to - level_from <= stage_levels() (the walker keeps 8 bits per     */
+/*     depth in one 32-bit word): the rule of kamd_gs_to_spc_stage_*.           */
 /*  3. build: stable sort by code, first triangle of every voxel, all octree    */
 /*     levels, into the workspace; sizes[0] = voxels, sizes[1 + l] = nodes of   */
 /*     octree level l (device int64[1 + level], read by the host).              */

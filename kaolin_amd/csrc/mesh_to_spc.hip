@@ -118,6 +118,10 @@ struct MsPrim {
   __device__ __forceinline__ bool test(const Data& d, int x, int y, int z, int level) const { return ms_test(d, x, y, z, level); }
 };
 constexpr int64_t MS_NO_TOTAL = INT64_MAX;  // the emit pass writes exactly the slots the count pass summed
+// the walker keeps 8 bits per depth in one 32-bit word: a wider span would shift by 32 and more (the rule of gs_to_spc.hip)
+inline bool ms_stage_span_ok(int level_from, int level_to) {
+  return level_from >= 0 && level_to >= level_from && level_to <= MS_MAX_LEVEL && level_to - level_from <= MS_STAGE_LEVELS;
+}
 
 // after the sort: one voxel (its first, i.e. smallest, triangle) per run of equal codes; sizes[0] = voxels
 __global__ __launch_bounds__(256) void ms_unique_kernel(int64_t n, const int64_t* __restrict__ m, const int64_t* __restrict__ t,
@@ -241,7 +245,7 @@ int kamd_mesh_to_spc_stage_count(void* stream, int64_t n, const float* face_vert
                                  const int64_t* triangle_id, int level_from, int level_to, int tested, int32_t* counts,
                                  int64_t* offsets, void* scan_workspace) {
   if (n <= 0) return 0;
-  if (level_from < 0 || level_to < level_from || level_to > MS_MAX_LEVEL) return (int)hipErrorInvalidValue;
+  if (!ms_stage_span_ok(level_from, level_to)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   kamd::ProfScope prof_(kamd::K_SPC_STAGE, st);
   hipLaunchKernelGGL((spc_stage_kernel<false, MsPrim>), dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, MsPrim{face_vertices}, morton,
@@ -254,6 +258,7 @@ int kamd_mesh_to_spc_stage_emit(void* stream, int64_t n, const float* face_verti
                                 const int64_t* triangle_id, int level_from, int level_to, int tested, const int64_t* offsets,
                                 int64_t* morton_out, int64_t* triangle_id_out) {
   if (n <= 0) return 0;
+  if (!ms_stage_span_ok(level_from, level_to)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   kamd::ProfScope prof_(kamd::K_SPC_STAGE, st);
   hipLaunchKernelGGL((spc_stage_kernel<true, MsPrim>), dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, MsPrim{face_vertices}, morton,
