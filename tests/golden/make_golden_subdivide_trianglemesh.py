@@ -28,6 +28,11 @@ function).  No stored row is NaN (asserted).
               (asserted to bound the float64 gradient of the package's torch formulation)
   dtypes_*    the dtypes the reference returns where it accepts the arguments
   err_*       type and text of what the reference raises for arguments it does not accept
+
+A second file, tests/golden/subdivide_trianglemesh_edges.npz (``main_edges``), holds small meshes at the valences and edge counts
+the first has none of (``small_cases``): wheels of 3 .. 300 rim vertices with the hub as the first or the last id, one triangle,
+the faces (a, b, a) and (a, a, a), triangles repeated up to an edge of count 4, and a tetrahedron that skips an id.  It draws from
+a generator of its own, so the first file comes out byte for byte as before.
 """
 import os
 import sys
@@ -46,6 +51,7 @@ from kaolin_amd.utils.testing import geodesic_sphere  # noqa: E402
 
 SPARSE_V = 70001
 NAME = 'subdivide_trianglemesh.npz'
+EDGES_NAME = 'subdivide_trianglemesh_edges.npz'
 
 
 def load_modules():
@@ -262,5 +268,73 @@ def main():
             print(k, list(out[k]))
 
 
+def wheel(n, hub_last):
+    """n rim vertices around a hub, n faces (hub, rim i, rim i + 1): the hub has valence n and its n spokes have count 2; the rim
+    is a boundary.  Hub as id 0: its n edges are one run of the edge list; hub as id n: one run of the transposed list."""
+    rim = torch.arange(n) + (0 if hub_last else 1)
+    hub = torch.full((n,), n if hub_last else 0)
+    return torch.stack((hub, rim, rim.roll(-1)), dim=1)
+
+
+def small_cases():
+    """name -> (faces, V) of every case of the second file, in order"""
+    cases = {}
+    for n in (3, 4, 6, 255, 256, 257, 300):
+        cases[f'wheel{n}_hub_first'], cases[f'wheel{n}_hub_last'] = (wheel(n, False), n + 1), (wheel(n, True), n + 1)
+    cases['triangle'] = (torch.tensor([[0, 1, 2]]), 3)                                    # valence 2, counts 1
+    cases['aba'] = (torch.tensor([[1, 0, 1]]), 2)         # id 0 has valence 1; edge (0, 1) has count 2, corners (1, 1); (1, 1)
+    cases['aaa'] = (torch.tensor([[0, 0, 0]]), 1)                                         # E = 1, count 3
+    t1, t2 = [0, 1, 2], [2, 1, 3]
+    cases['pair4'] = (torch.tensor([t1, t2, [1, 3, 2], [3, 2, 1]]), 4)                    # t2 three times: counts 1, 3 and 4
+    cases['counts234'] = (torch.tensor([t1, t2, [1, 3, 2], [2, 3, 4], [4, 2, 3]]), 5)     # t2 and (2, 3, 4) twice: counts 1 .. 4
+    cases['tet_gap'] = (torch.tensor([[0, 1, 3], [0, 1, 4], [0, 3, 4], [1, 3, 4]]), 5)    # id 2 is unused
+    return cases
+
+
+def main_edges():
+    """tests/golden/subdivide_trianglemesh_edges.npz: small meshes at the valences and counts the first file does not hold, one
+    iteration, B = 1, float32, both settings, stored as the first file stores its cases (``<case>_vertices``, ``_faces``,
+    ``_alpha``, ``<case>_slots_1``, ``<case>_<setting>_1_vertices``).  Where the reference returns NaN in a row (an unused id), the
+    row is stored as zeros and ``<case>_<setting>_1_nanrows`` (bool per row) marks it; where it raises, ``err_<case>_<setting>``
+    holds the type and the text and nothing else is stored for that setting: no value is recorded for what the reference does
+    not define."""
+    tm, _ = load_modules()
+    g = torch.Generator().manual_seed(20263)
+    out = {}
+    for case, (faces, V) in small_cases().items():
+        vertices = torch.rand(1, V, 3, generator=g) - 0.5
+        alpha = torch.rand(1, V, generator=g)
+        out[f'{case}_vertices'], out[f'{case}_faces'], out[f'{case}_alpha'] = vertices.numpy(), compact(faces), alpha.numpy()
+        topo = None
+        for setting, a in (('default', None), ('alpha', alpha)):
+            try:
+                nv, nf = tm.subdivide_trianglemesh(vertices, faces, 1, a)
+            except Exception as err:  # noqa: BLE001  (the reference's own error, whatever its type)
+                out[f'err_{case}_{setting}'] = np.array([type(err).__name__, str(err)])
+                continue
+            assert nv.dtype == torch.float32 and nf.dtype == torch.long and nf.shape == (faces.shape[0] * 4, 3)
+            assert topo is None or torch.equal(topo, nf)
+            topo = nf
+            nan_rows = torch.isnan(nv[0]).any(dim=1)
+            if bool(nan_rows.any()):
+                out[f'{case}_{setting}_1_nanrows'] = nan_rows.numpy()
+                nv = torch.where(nan_rows[None, :, None], torch.zeros_like(nv), nv)
+            assert not bool(torch.isnan(nv).any())
+            out[f'{case}_{setting}_1_vertices'] = nv.numpy()
+        if topo is not None:
+            slots = torch.stack([topo[1::4, 1], topo[0::4, 1], topo[1::4, 2]], dim=1)               # ab, bc, ca
+            assert torch.equal(child_faces(faces, slots), topo)
+            out[f'{case}_slots_1'] = compact(slots)
+    path = os.path.join(HERE, EDGES_NAME)
+    np.savez_compressed(path, **out)
+    print('wrote', EDGES_NAME, len(out), 'arrays', os.path.getsize(path), 'bytes')
+    for k in sorted(out):
+        if k.startswith('err_'):
+            print(k, list(out[k]))
+        elif k.endswith('_nanrows'):
+            print(k, int(out[k].sum()), 'of', out[k].size, 'rows')
+
+
 if __name__ == '__main__':
     main()
+    main_edges()

@@ -1,6 +1,7 @@
-"""What test_subdivide_trianglemesh_cpu.py and test_subdivide_trianglemesh_gpu.py share: the reference's recorded answers
-(tests/golden/subdivide_trianglemesh.npz, written by make_golden_subdivide_trianglemesh.py) decoded into inputs and expected
-tensors.  The reference computes in float32 and for one item at a time; every record is float32."""
+"""What the subdivide_trianglemesh test files share: the reference's recorded answers (tests/golden/subdivide_trianglemesh.npz
+and, for the small meshes at the bottom, subdivide_trianglemesh_edges.npz; both written by
+make_golden_subdivide_trianglemesh.py) decoded into inputs and expected tensors.  The reference computes in float32 and for one
+item at a time; every record is float32."""
 import os
 
 import numpy as np
@@ -92,6 +93,38 @@ def check_forward(case, iterations, setting, new_vertices, new_faces, tol=1e-5, 
     if verbose:
         print(case, iterations, setting, 'max abs diff', float((recorded.double() - want.double()).abs().max()), msg)
     assert msg is None, msg
+
+
+# ---- the second file: small meshes at the valences and edge counts the first has none of (one iteration, B = 1) ----------------
+G_SMALL = np.load(os.path.join(GOLDEN_DIR, 'subdivide_trianglemesh_edges.npz'))
+SMALL_CASES = [name[:-len('_faces')] for name in G_SMALL.files if name.endswith('_faces')]
+
+
+def small_inputs(case):
+    """-> vertices (1, V, 3) float32, faces (F, 3) int64, alpha (1, V) float32 of a case of the second file"""
+    return (torch.from_numpy(G_SMALL[f'{case}_vertices']), torch.from_numpy(G_SMALL[f'{case}_faces']).long(),
+            torch.from_numpy(G_SMALL[f'{case}_alpha']))
+
+
+def check_small_forward(case, setting, new_vertices, new_faces, tol=1e-5):
+    """check_forward for a case of the second file: the faces, and every row the reference defines (it returns NaN for the row of
+    an unused id: those rows are marked, not recorded, and must be the inputs, bit for bit) -> the number of rows compared"""
+    from kaolin_amd.utils.testing import elementwise_mismatch
+    assert f'err_{case}_{setting}' not in G_SMALL.files                   # (the reference raised for none of them)
+    vertices, faces, _ = small_inputs(case)
+    new_vertices, new_faces = new_vertices.detach().cpu(), new_faces.cpu()
+    slots = torch.from_numpy(G_SMALL[f'{case}_slots_1']).long()
+    assert new_faces.dtype == torch.long and torch.equal(new_faces, child_faces(faces, slots)), case
+    want = torch.from_numpy(G_SMALL[f'{case}_{setting}_1_vertices'])
+    defined = torch.ones(want.shape[1], dtype=torch.bool)
+    if f'{case}_{setting}_1_nanrows' in G_SMALL.files:
+        defined = ~torch.from_numpy(G_SMALL[f'{case}_{setting}_1_nanrows'])
+        rest = torch.nonzero(~defined).reshape(-1)
+        assert int(rest.max()) < vertices.shape[1] and torch.equal(new_vertices[:, rest], vertices[:, rest].to(new_vertices.dtype))
+    assert not bool(torch.isnan(want).any())
+    msg = elementwise_mismatch(new_vertices[:, defined], want[:, defined], tol=tol)
+    assert msg is None, (case, setting, msg)
+    return int(defined.sum())
 
 
 def check_gradients(case, grad_vertices, grad_alpha, verbose=False):
