@@ -60,8 +60,10 @@ def _edge_test(c0, c1, c2, c3, c4, c5, iso, s, t, lo, hi):
     return (d > 0) & ~((hi.astype(F64) <= r0) | (r1 <= lo.astype(F64)))
 
 
-def _face_test(p, q, vs, i, j, k, o):
+def _face_test(p, q, vs, i, j, k, o, operands=None):
     t = ((q[:, i] - (p[:, i] + o)).astype(F64) / (2.0 * q[:, i].astype(F64))).astype(F32)
+    if operands is not None:
+        operands.append(t)
     ok = (F32(0) <= t) & (t <= F32(1))
     f = 1.0 - 2.0 * t.astype(F64)
     hj = (f * q[:, j].astype(F64)).astype(F32)
@@ -69,8 +71,9 @@ def _face_test(p, q, vs, i, j, k, o):
     return ok & (p[:, j] <= hj) & (hj <= p[:, j] + vs) & (p[:, k] <= hk) & (hk <= p[:, k] + vs)
 
 
-def decide(g, gid, level, means, cov, ab0, ab1, cp, iso):
-    """GSVoxelInOut for the voxels g (n, 3) at `level` against the Gaussians gid (n) -> bool (n)"""
+def decide(g, gid, level, means, cov, ab0, ab1, cp, iso, face_operands=None):
+    """GSVoxelInOut for the voxels g (n, 3) at `level` against the Gaussians gid (n) -> bool (n).  `face_operands`: a list that
+    receives the operand t of the six face tests, float32 (n) each, axis by axis, the lower face first"""
     vs = _voxel_size(level)
     with np.errstate(all='ignore'):
         v = g.astype(F32) * vs + F32(-1.0)          # == fmaf(g, vs, -1): g * vs is exact (vs is a power of two)
@@ -81,7 +84,7 @@ def decide(g, gid, level, means, cov, ab0, ab1, cp, iso):
         face = np.zeros(len(g), bool)
         for i, j, k in ((0, 1, 2), (1, 0, 2), (2, 0, 1)):
             for o in (F32(0), vs):
-                face |= _face_test(p, cp[gid, i], vs, i, j, k, o)
+                face |= _face_test(p, cp[gid, i], vs, i, j, k, o, face_operands)
         C = [cov[gid, k] for k in range(6)]
         edge = np.zeros(len(g), bool)
         for i in range(4):
@@ -124,6 +127,36 @@ def gs_to_spc(means, scales, rots, iso, tol, level):
     boundary = np.ones(len(m), bool)
     boundary[1:] = m[1:] != m[:-1]
     return g.astype(np.int16), gid, boundary, cov
+
+
+def subtree(means, cov, ab0, ab1, cp, iso, codes, gid, level_from, level_to, tested):
+    """One stage.  Proposal i is the voxel codes[i] (Morton) of `level_from` with the Gaussian gid[i]; cov, ab0, ab1, cp come from
+    ``prepare`` at the target level of the whole conversion (the clamp does not follow the stage).
+    -> (counts (n), out_codes, out_gid): for every proposal, in proposal order, the ascending Morton codes at `level_to` that pass
+    ``decide`` with all their ancestors down from `level_from` (its own level included unless `tested`), and the proposal's Gaussian."""
+    means = np.ascontiguousarray(means, dtype=F32)
+    code = np.asarray(codes, dtype=np.int64).copy()
+    gid = np.asarray(gid, dtype=np.int64)
+    owner = np.arange(len(code), dtype=np.int64)
+
+    def keep(code, owner, l):
+        if len(code) == 0:
+            return code, owner
+        g = np.zeros((len(code), 3), np.int64)
+        for b in range(15):
+            for axis in range(3):
+                g[:, axis] |= ((code >> (3 * b + 2 - axis)) & 1) << b
+        ok = decide(g, gid[owner], l, means, cov, ab0, ab1, cp, iso)
+        return code[ok], owner[ok]
+
+    if not tested:
+        code, owner = keep(code, owner, int(level_from))
+    for l in range(int(level_from) + 1, int(level_to) + 1):
+        code = (code[:, None] * 8 + np.arange(8, dtype=np.int64)[None]).reshape(-1)   # child k: x = bit 2, y = bit 1, z = bit 0
+        owner = np.repeat(owner, 8)
+        code, owner = keep(code, owner, l)
+    counts = np.bincount(owner, minlength=len(gid)).astype(np.int64)
+    return counts, code, gid[owner]
 
 
 def integrate_gs(points, gaus_id, means, cov, opacities, level, step, chunk=4096):
