@@ -18,6 +18,7 @@
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "sort_scan.h"
 #include "spc_stage.h"
 #include "../../include/kaolin_amd.h"
 
@@ -171,12 +172,12 @@ __global__ __launch_bounds__(256) void gs_points_kernel(int64_t n, const int64_t
   boundary[i] = flag[i] ? 1 : 0;
 }
 
-// workspace of kamd_gs_to_spc_finish for n pairs: keys A (n) | vals A (n) | keys B (n) | flag (n ints) | the sort's (digit, block)
-// counts (256 * blocks ints), their offsets (256 * blocks + 1) and scan sums
+// workspace of kamd_gs_to_spc_finish for n pairs: keys A (n) | vals A (n) | keys B (n) | flag (n ints) | the sort's scratch
+// (sort_scan_host.h): (digit, block) counts (ints), their offsets and scan sums
 struct GsWs {
   int64_t *ka, *va, *kb;
   int* flag;
-  SpcSortWs sort;
+  SsSortWs sort;
   size_t total_bytes;
 };
 GsWs gs_ws(void* base, int64_t n) {
@@ -192,10 +193,9 @@ GsWs gs_ws(void* base, int64_t n) {
   w.va = (int64_t*)take(n1 * 8);
   w.kb = (int64_t*)take(n1 * 8);
   w.flag = (int*)take(n1 * 4);
-  const size_t hn = spc_sort_hist_entries(n);
-  w.sort.hist = (int*)take(hn * 4);
-  w.sort.offs = (int64_t*)take((hn + 1) * 8);
-  w.sort.sums = (int64_t*)take((hn / 1024 + 2) * 8);
+  w.sort.hist = (int*)take(ss_sort_hist_entries(n) * 4);
+  w.sort.offs = (long long*)take(ss_sort_offs_entries(n) * 8);
+  w.sort.sums = (long long*)take(ss_sort_sums_entries(n) * 8);
   w.total_bytes = (size_t)(p - (char*)base);
   return w;
 }
@@ -266,7 +266,7 @@ int kamd_gs_to_spc_prepare(void* stream, int64_t G, const float* means3D, const 
   KAMD_RETURN_LAST_ERROR();
 }
 
-size_t kamd_gs_to_spc_scan_workspace(int64_t n) { return ((size_t)(n > 0 ? n : 0) / 1024 + 2) * 8; }
+size_t kamd_gs_to_spc_scan_workspace(int64_t n) { return ss_scan_sums_entries(n) * 8; }
 
 int kamd_gs_to_spc_stage_count(void* stream, int64_t n, int64_t G, const float* means3D, const float* cov3d_invs,
                                const void* prepared, float iso, const int64_t* morton, const int64_t* gaus_id, int level_from,
@@ -279,7 +279,7 @@ int kamd_gs_to_spc_stage_count(void* stream, int64_t n, int64_t G, const float* 
   hipLaunchKernelGGL((spc_stage_kernel<false, GsPrim>), dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, prim, morton, gaus_id,
                      level_from, level_to, tested, counts, (const int64_t*)nullptr, (int64_t)0, (int64_t*)nullptr,
                      (int64_t*)nullptr);
-  return ms_scan(st, n, nullptr, counts, offsets, (int64_t*)scan_workspace);
+  return ss_scan(st, n, (const int64_t*)nullptr, counts, offsets, (int64_t*)scan_workspace);
 }
 
 int kamd_gs_to_spc_stage_emit(void* stream, int64_t n, int64_t G, const float* means3D, const float* cov3d_invs,
@@ -306,10 +306,9 @@ int kamd_gs_to_spc_finish(void* stream, int64_t n, int level, const int64_t* mor
   hipStream_t st = (hipStream_t)stream;
   const GsWs w = gs_ws(workspace, n);
   if (workspace == nullptr || workspace_bytes < w.total_bytes) return (int)hipErrorInvalidValue;
-  KAMD_CHECK(spc_sort_pairs(st, n, 3 * level, (const uint64_t*)morton, gaus_id, (uint64_t*)w.ka, w.va, (uint64_t*)w.kb, gaus_id_out,
-                            w.sort));
+  KAMD_CHECK(ss_sort(st, n, ss_passes_low(3 * level), morton, gaus_id, w.ka, w.va, w.kb, gaus_id_out, w.sort));
   const unsigned g = (unsigned)kamd_cdiv(n, 256);
-  hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)nullptr, (const int64_t*)w.kb, 0, w.flag);
+  KAMD_CHECK(ss_heads(st, n, (const int64_t*)nullptr, w.kb, 0, w.flag));
   hipLaunchKernelGGL(gs_points_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)w.kb, (const int*)w.flag, (short*)points,
                      (unsigned char*)pack_boundary);
   KAMD_RETURN_LAST_ERROR();

@@ -14,14 +14,14 @@
 //   2. mt_classify_kernel    THE pass over `tets` (32 bytes per tet as two 16-byte loads): the case of every tet as one byte,
 //                            and per chunk of 1 024 tets the number of one- and two-triangle tets.  A tet with a corner outside
 //                            [0, V) is case 0: nothing downstream ever indexes with an id this kernel has not compared with V.
-//   3. mt_scan               exclusive scan of the chunk counts (both kinds in one array); the HOST reads the two totals.
+//   3. ss_scan               exclusive scan of the chunk counts (both kinds in one array); the HOST reads the two totals.
 //   4. mt_compact_kernel     re-reads the case bytes (1 byte per tet), ranks the valid tets of a chunk in tet order (ballots
 //                            inside a wavefront, LDS across wavefronts) and writes (tet << 4 | case) into the one- or the
 //                            two-triangle list, plus one key (a << 32 | b) per crossing edge of the tet (3 or 4).
 //   5. sort                  stable 8-bit LSD radix sort of the keys alone (histogram per block of 2 048, one scan over the
 //                            (digit, block) counts, ranked scatter), over the digits below ceil(log2 V) of either half only.
-//   6. mt_heads / mt_unique  first of every run of equal keys, scan, compaction: the unique keys ARE the vertex list; the HOST
-//                            reads their number.
+//   6. ss_unique             first of every run of equal keys, scan, compaction: the unique keys ARE the vertex list; the HOST
+//                            reads their number.  (5 and 6: sort_scan.h)
 //   7. mt_verts_kernel       per unique edge: the vertex and the (a, b) pair autograd keeps.
 //      mt_faces_kernel       per valid tet: its rows of `faces` (and `tet_idx`); the rank of each of its crossing edges by
 //                            binary search in the unique keys.
@@ -32,7 +32,8 @@
 // Result sizes depend on the data: the two host reads synchronise the stream, so the operator cannot be captured in a graph
 // (neither can the reference: torch.unique and boolean indexing synchronise).
 #include "common.h"
-#include "tet_sort.h"
+#include "sort_scan.h"
+#include "tet_load.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
@@ -58,27 +59,25 @@ struct MtLayout {
 };
 MtLayout mt_layout(long long T, long long V) {
   MtLayout l;
-  l.nchunk = mt_cdiv(T, MT_CHUNK);
-  l.words = mt_cdiv(V, 64);
+  l.nchunk = ss_cdiv(T, MT_CHUNK);
+  l.words = ss_cdiv(V, 64);
   size_t o = 0;
   l.bitmap = o, o += mt_align((size_t)l.words * 8);
   l.cases = o, o += mt_align((size_t)T);
   l.counts = o, o += mt_align((size_t)l.nchunk * 2 * 4);
   l.offs = o, o += mt_align(((size_t)l.nchunk * 2 + 1) * 8);
-  l.sums = o, o += mt_align(((size_t)mt_cdiv(l.nchunk * 2, 1024) + 1) * 8);
+  l.sums = o, o += mt_align(ss_scan_sums_entries(l.nchunk * 2) * 8);
   l.bytes = o;
   return l;
 }
 // ---- the edge workspace, sized by the two counts the host has read -------------------------------------------------------
 struct MtEdgeLayout {
-  long long n, nsb;  // crossing-edge instances, sort blocks
+  long long n;  // crossing-edge instances
   size_t entries, keys_a, keys_b, uniq, flags, pos, hist, hoffs, sums, bytes;
 };
 MtEdgeLayout mt_edge_layout(long long n_one, long long n_two) {
   MtEdgeLayout l;
   l.n = 3 * n_one + 4 * n_two;
-  l.nsb = mt_cdiv(l.n, MT_SORT_BLOCK);
-  const long long scan_max = l.nsb * 256 > l.n ? l.nsb * 256 : l.n;
   size_t o = 0;
   l.entries = o, o += mt_align((size_t)(n_one + n_two) * 8);
   l.keys_a = o, o += mt_align((size_t)l.n * 8);
@@ -86,9 +85,9 @@ MtEdgeLayout mt_edge_layout(long long n_one, long long n_two) {
   l.uniq = o, o += mt_align((size_t)l.n * 8);
   l.flags = o, o += mt_align((size_t)l.n * 4);
   l.pos = o, o += mt_align(((size_t)l.n + 1) * 8);
-  l.hist = o, o += mt_align((size_t)l.nsb * 256 * 4);
-  l.hoffs = o, o += mt_align(((size_t)l.nsb * 256 + 1) * 8);
-  l.sums = o, o += mt_align(((size_t)mt_cdiv(scan_max, 1024) + 1) * 8);
+  l.hist = o, o += mt_align(ss_sort_hist_entries(l.n) * 4);
+  l.hoffs = o, o += mt_align(ss_sort_offs_entries(l.n) * 8);
+  l.sums = o, o += mt_align(ss_sort_unique_sums_entries(l.n) * 8);
   l.bytes = o;
   return l;
 }
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(256) void mt_faces_kernel(long long n_one, long lon
     if (((c >> i) ^ (c >> j)) & 1u) {
       const unsigned long long a = tet.id[i] < tet.id[j] ? tet.id[i] : tet.id[j];
       const unsigned long long b = tet.id[i] < tet.id[j] ? tet.id[j] : tet.id[i];
-      rk[s] = mt_rank(uniq, nu, (a << 32) | b);
+      rk[s] = ss_rank(uniq, nu, (a << 32) | b);
     }
   }
   const bool two = e >= n_one;
@@ -303,13 +302,13 @@ int mt_classify(hipStream_t st, long long nt, long long V, const int64_t* tets, 
   unsigned long long* bitmap = (unsigned long long*)(ws + l.bitmap);
   int* counts = (int*)(ws + l.counts);
   long long* offs = (long long*)(ws + l.offs);
-  long long blocks = mt_cdiv(l.words, MT_THREADS / 64);
+  long long blocks = ss_cdiv(l.words, MT_THREADS / 64);
   if (blocks > (long long)KAMD_NUM_CU * 8) blocks = (long long)KAMD_NUM_CU * 8;
   hipLaunchKernelGGL((mt_occupancy_kernel<T>), dim3((unsigned)blocks), dim3(MT_THREADS), 0, st, sdf, V, l.words, bitmap);
   hipLaunchKernelGGL(mt_classify_kernel, dim3((unsigned)l.nchunk), dim3(MT_THREADS), 0, st, tets, nt, (unsigned long long)V,
                      (const unsigned long long*)bitmap, (unsigned char*)(ws + l.cases), counts, l.nchunk);
   KAMD_CHECK(hipGetLastError());
-  KAMD_CHECK(mt_scan(st, 2 * l.nchunk, counts, offs, (long long*)(ws + l.sums)));
+  KAMD_CHECK(ss_scan(st, 2 * l.nchunk, (const long long*)nullptr, counts, offs, (long long*)(ws + l.sums)));
   long long h[2] = {0, 0};
   KAMD_CHECK(hipMemcpyAsync(&h[0], offs + l.nchunk, 8, hipMemcpyDeviceToHost, st));
   KAMD_CHECK(hipMemcpyAsync(&h[1], offs + 2 * l.nchunk, 8, hipMemcpyDeviceToHost, st));
@@ -341,42 +340,16 @@ int mt_edges(hipStream_t st, long long nt, long long V, const int64_t* tets, con
   char* ews = (char*)edges_workspace;
   unsigned long long* keys = (unsigned long long*)(ews + el.keys_a);
   unsigned long long* other = (unsigned long long*)(ews + el.keys_b);
-  unsigned long long* uniq = (unsigned long long*)(ews + el.uniq);
-  int* flags = (int*)(ews + el.flags);
-  long long* pos = (long long*)(ews + el.pos);
-  int* hist = (int*)(ews + el.hist);
-  long long* hoffs = (long long*)(ews + el.hoffs);
   long long* sums = (long long*)(ews + el.sums);
 
   hipLaunchKernelGGL(mt_compact_kernel, dim3((unsigned)l.nchunk), dim3(MT_THREADS), 0, st, tets, nt,
                      (const unsigned char*)(ws + l.cases), (const long long*)(ws + l.offs), l.nchunk, n_one,
                      (unsigned long long*)(ews + el.entries), keys);
   KAMD_CHECK(hipGetLastError());
-
-  const int nb = mt_id_bits(V);
-  for (int half = 0; half < 2; ++half) {
-    for (int shift = 0; shift < nb; shift += 8) {
-      hipLaunchKernelGGL(mt_sort_hist_kernel, dim3((unsigned)el.nsb), dim3(256), 0, st, el.n, (const unsigned long long*)keys,
-                         32 * half + shift, el.nsb, hist);
-      KAMD_CHECK(mt_scan(st, el.nsb * 256, hist, hoffs, sums));
-      hipLaunchKernelGGL(mt_sort_scatter_kernel, dim3((unsigned)el.nsb), dim3(256), 0, st, el.n, (const unsigned long long*)keys,
-                         32 * half + shift, el.nsb, (const long long*)hoffs, other);
-      unsigned long long* tmp = keys;
-      keys = other;
-      other = tmp;
-    }
-  }
-  KAMD_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(mt_heads_kernel, dim3(mt_grid(el.n, 256)), dim3(256), 0, st, el.n, (const unsigned long long*)keys, flags);
-  KAMD_CHECK(mt_scan(st, el.n, flags, pos, sums));
-  hipLaunchKernelGGL(mt_unique_kernel, dim3(mt_grid(el.n, 256)), dim3(256), 0, st, el.n, (const unsigned long long*)keys,
-                     (const int*)flags, (const long long*)pos, uniq);
-  KAMD_CHECK(hipGetLastError());
-  long long h = 0;
-  KAMD_CHECK(hipMemcpyAsync(&h, pos + el.n, 8, hipMemcpyDeviceToHost, st));
-  KAMD_CHECK(hipStreamSynchronize(st));
-  *host_num_unique = h;
-  return 0;
+  KAMD_CHECK(ss_sort(st, el.n, ss_passes_halves(mt_id_bits(V)), keys, other, keys,  // in place, through `other`
+                     ss_sort_ws((int*)(ews + el.hist), (long long*)(ews + el.hoffs), sums)));
+  return ss_unique(st, el.n, keys, (int*)(ews + el.flags), (long long*)(ews + el.pos), sums,
+                   (unsigned long long*)(ews + el.uniq), host_num_unique);
 }
 
 template <typename T>
@@ -390,8 +363,8 @@ int mt_emit(hipStream_t st, long long V, const int64_t* tets, const T* vertices,
   const MtEdgeLayout el = mt_edge_layout(n_one, n_two);
   const char* ews = (const char*)edges_workspace;
   const unsigned long long* uniq = (const unsigned long long*)(ews + el.uniq);
-  hipLaunchKernelGGL((mt_verts_kernel<T>), dim3(mt_grid(nu, 256)), dim3(256), 0, st, nu, uniq, vertices, sdf, verts, edges);
-  hipLaunchKernelGGL(mt_faces_kernel, dim3(mt_grid(n_one + n_two, 256)), dim3(256), 0, st, n_one, n_two,
+  hipLaunchKernelGGL((mt_verts_kernel<T>), dim3(ss_grid(nu, 256)), dim3(256), 0, st, nu, uniq, vertices, sdf, verts, edges);
+  hipLaunchKernelGGL(mt_faces_kernel, dim3(ss_grid(n_one + n_two, 256)), dim3(256), 0, st, n_one, n_two,
                      (const unsigned long long*)(ews + el.entries), tets, uniq, nu, faces, tet_idx);
   KAMD_RETURN_LAST_ERROR();
 }
@@ -404,7 +377,7 @@ int mt_backward(hipStream_t st, long long nu, long long V, const int64_t* edges,
   if (edges == nullptr || vertices == nullptr || sdf == nullptr || grad_verts == nullptr || grad_vertices == nullptr ||
       grad_sdf == nullptr)
     return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((mt_backward_kernel<T>), dim3(mt_grid(nu, 256)), dim3(256), 0, st, nu, (unsigned long long)V, edges, vertices,
+  hipLaunchKernelGGL((mt_backward_kernel<T>), dim3(ss_grid(nu, 256)), dim3(256), 0, st, nu, (unsigned long long)V, edges, vertices,
                      sdf, grad_verts, grad_vertices, grad_sdf);
   KAMD_RETURN_LAST_ERROR();
 }

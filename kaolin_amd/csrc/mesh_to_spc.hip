@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "common.h"
 #include "profile.h"
+#include "sort_scan.h"
 #include "spc_octree.h"
 #include "spc_stage.h"
 #include "../../include/kaolin_amd.h"
@@ -32,7 +33,8 @@ namespace {
 constexpr int MS_STAGE_LEVELS = 3;   // levels finished per stage below the proposal's own
 constexpr int MS_MAX_LEVEL = 15;     // KAOLIN_SPC_MAX_LEVELS (spc_math.h:38)
 
-// (the Morton layout, the scan, the run heads, the parents and the octree gather live in spc_octree.h, shared with spc.hip)
+// (the Morton layout, the parents and the octree gather live in spc_octree.h, shared with spc.hip; the scan, the sort and the run
+// heads in sort_scan.h)
 struct MsTri {
   float a[3], b[3], c[3];
 };
@@ -106,7 +108,7 @@ __device__ __forceinline__ bool ms_test(const MsTri& t, int x, int y, int z, int
 
 // ---- a stage: every proposal (voxel at level_from, triangle) walks its subtree down to level_to: spc_stage_kernel of spc_stage.h
 // (eight lanes per proposal, three levels in registers) with the triangle as its primitive.  The stable radix sort of (Morton code,
-// triangle) pairs by code is spc_sort_pairs of the same header (the reference sorts with thrust, mesh_to_spc_cuda.cu:388-392): equal
+// triangle) pairs by code is ss_sort of sort_scan.h (the reference sorts with thrust, mesh_to_spc_cuda.cu:388-392): equal
 // codes keep their order -- triangles ascending inside a voxel, which is what picks a voxel's face.
 struct MsPrim {
   typedef MsTri Data;
@@ -196,14 +198,13 @@ __global__ __launch_bounds__(256) void ms_results_kernel(int64_t nvox, int level
 
 // workspace of kamd_mesh_to_spc_build for n pairs at `level` (8-byte words unless noted):
 //   sizes (16) | sorted morton (n) | sorted tri (n) | unique morton A (n) | unique tri (n) | morton B (n) | pos (n + 1)
-//   | scan sums (n / 1024 + 2) | flag (n ints) | level bytes (level * n)
-//   | the sort's (digit, block) counts (256 * blocks ints), their offsets (256 * blocks + 1) and scan sums
+//   | scan sums | flag (n ints) | level bytes (level * n)
+//   | the sort's scratch (sort_scan_host.h): (digit, block) counts (ints), their offsets and scan sums
 struct MsWs {
   int64_t *sizes, *sm, *st, *um, *ut, *mb, *pos, *sums;
   int* flag;
   unsigned char* level_bytes;
-  int* sort_hist;
-  int64_t *sort_offs, *sort_sums;
+  SsSortWs sort;
   size_t total_bytes;
 };
 MsWs ms_ws(void* base, int64_t n, int level) {
@@ -222,13 +223,12 @@ MsWs ms_ws(void* base, int64_t n, int level) {
   w.ut = (int64_t*)take(n8);
   w.mb = (int64_t*)take(n8);
   w.pos = (int64_t*)take(n8 + 8);
-  w.sums = (int64_t*)take(((size_t)n / 1024 + 2) * 8);
+  w.sums = (int64_t*)take(ss_scan_sums_entries(n) * 8);
   w.flag = (int*)take((size_t)(n > 0 ? n : 1) * 4);
   w.level_bytes = (unsigned char*)take((size_t)(level > 0 ? level : 1) * (size_t)(n > 0 ? n : 1));
-  const size_t hn = spc_sort_hist_entries(n);
-  w.sort_hist = (int*)take(hn * 4);
-  w.sort_offs = (int64_t*)take((hn + 1) * 8);
-  w.sort_sums = (int64_t*)take((hn / 1024 + 2) * 8);
+  w.sort.hist = (int*)take(ss_sort_hist_entries(n) * 4);
+  w.sort.offs = (long long*)take(ss_sort_offs_entries(n) * 8);
+  w.sort.sums = (long long*)take(ss_sort_sums_entries(n) * 8);
   w.total_bytes = (size_t)(p - (char*)base);
   return w;
 }
@@ -239,7 +239,7 @@ extern "C" {
 
 int kamd_mesh_to_spc_stage_levels(void) { return MS_STAGE_LEVELS; }
 
-size_t kamd_mesh_to_spc_scan_workspace(int64_t n) { return ((size_t)(n > 0 ? n : 0) / 1024 + 2) * 8; }
+size_t kamd_mesh_to_spc_scan_workspace(int64_t n) { return ss_scan_sums_entries(n) * 8; }
 
 int kamd_mesh_to_spc_stage_count(void* stream, int64_t n, const float* face_vertices, const int64_t* morton,
                                  const int64_t* triangle_id, int level_from, int level_to, int tested, int32_t* counts,
@@ -251,7 +251,7 @@ int kamd_mesh_to_spc_stage_count(void* stream, int64_t n, const float* face_vert
   hipLaunchKernelGGL((spc_stage_kernel<false, MsPrim>), dim3(kamd_cdiv(n * 8, 256)), dim3(256), 0, st, n, MsPrim{face_vertices}, morton,
                      triangle_id, level_from, level_to, tested, counts, (const int64_t*)nullptr, MS_NO_TOTAL, (int64_t*)nullptr,
                      (int64_t*)nullptr);
-  return ms_scan(st, n, nullptr, counts, offsets, (int64_t*)scan_workspace);
+  return ss_scan(st, n, (const int64_t*)nullptr, counts, offsets, (int64_t*)scan_workspace);
 }
 
 int kamd_mesh_to_spc_stage_emit(void* stream, int64_t n, const float* face_vertices, const int64_t* morton,
@@ -279,11 +279,9 @@ int kamd_mesh_to_spc_build(void* stream, int64_t n, int level, const int64_t* mo
   kamd::ProfScope prof_(kamd::K_SPC_BUILD, st);
   // the sorted pairs land in (sm, st); (um, ut) is the other side of the ping-pong.  (level 0: a single voxel, every key is 0 and
   // the order is already by triangle: a copy)
-  KAMD_CHECK(spc_sort_pairs(st, n, 3 * level, (const uint64_t*)morton, triangle_id, (uint64_t*)w.um, w.ut, (uint64_t*)w.sm, w.st,
-                            SpcSortWs{w.sort_hist, w.sort_offs, w.sort_sums}));
+  KAMD_CHECK(ss_sort(st, n, ss_passes_low(3 * level), morton, triangle_id, w.um, w.ut, w.sm, w.st, w.sort));
   const unsigned g = (unsigned)kamd_cdiv(n, 256);
-  hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)nullptr, (const int64_t*)w.sm, 0, w.flag);
-  KAMD_CHECK(ms_scan(st, n, nullptr, w.flag, w.pos, w.sums));
+  KAMD_CHECK(ss_heads_scan(st, n, (const int64_t*)nullptr, w.sm, 0, w.flag, w.pos, w.sums));
   hipLaunchKernelGGL(ms_unique_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)w.sm, (const int64_t*)w.st,
                      (const int*)w.flag, (const int64_t*)w.pos, w.um, w.ut, w.sizes);
   // octree: level l nodes from the codes of level l + 1; counts stay on the device (grids sized by the bound n)
@@ -291,8 +289,7 @@ int kamd_mesh_to_spc_build(void* stream, int64_t n, int level, const int64_t* mo
   int64_t* nxt = w.mb;
   for (int l = level; l > 0; --l) {
     const int64_t* n_ptr = (l == level) ? w.sizes : w.sizes + 1 + l;  // nodes of level l (voxels at the deepest)
-    hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, (int64_t)0, n_ptr, (const int64_t*)cur, 3, w.flag);
-    KAMD_CHECK(ms_scan(st, n, n_ptr, w.flag, w.pos, w.sums));
+    KAMD_CHECK(ss_heads_scan(st, n, n_ptr, cur, 3, w.flag, w.pos, w.sums));
     hipLaunchKernelGGL(ms_parents_kernel, dim3(g), dim3(256), 0, st, n_ptr, (const int64_t*)cur, (const int*)w.flag,
                        (const int64_t*)w.pos, nxt, w.level_bytes + (size_t)(l - 1) * (size_t)n, w.sizes + 1 + (l - 1));
     // the first swap must not overwrite the unique voxel codes (needed by the results kernel): A -> B -> sorted -> B ...

@@ -4,7 +4,7 @@
 // The reference's versions are pure PyTorch (kaolin/ops/conversions/pointcloud.py): a row-wise unique, a sort, an index_add_ of
 // doubles (float atomics: the last bits change from run to run) and, for the grids, a unique over (B P, 4) int64 rows.  Here:
 //   * one thread per point quantises it (the operations of ops.spc.quantize_points, in their order) and writes (Morton key, index);
-//   * the stable pair sort of spc_stage.h orders the pairs by key: the members of a cell stay in ascending input index;
+//   * the stable pair sort of sort_scan.h orders the pairs by key: the members of a cell stay in ascending input index;
 //   * run heads, an exclusive scan and the run starts (U + 1);
 //   * the octree from the sorted keys through kamd_spc_octree_build (its own head / scan / unique pass drops the duplicates, so
 //     its ONE host read brings U and the level sizes together);
@@ -20,7 +20,8 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include "common.h"
-#include "spc_stage.h"
+#include "sort_scan.h"
+#include "spc_octree.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
@@ -87,7 +88,7 @@ struct PcWs {
   uint64_t *k0, *kt, *ks;
   int64_t *v0, *vt, *vs, *pos, *starts, *sums;
   int* flag;
-  SpcSortWs sort;
+  SsSortWs sort;
   void* octree;
   size_t octree_bytes, total_bytes;
 };
@@ -108,12 +109,11 @@ PcWs pc_ws(void* base, int64_t n, int level) {
   w.vs = (int64_t*)take(n1 * 8);
   w.pos = (int64_t*)take((n1 + 1) * 8);
   w.starts = (int64_t*)take((n1 + 1) * 8);
-  w.sums = (int64_t*)take((n1 / 1024 + 2) * 8);
+  w.sums = (int64_t*)take(ss_scan_sums_entries((long long)n1) * 8);
   w.flag = (int*)take(n1 * 4);
-  const size_t hn = spc_sort_hist_entries(n);
-  w.sort.hist = (int*)take(hn * 4);
-  w.sort.offs = (int64_t*)take((hn + 1) * 8);
-  w.sort.sums = (int64_t*)take((hn / 1024 + 2) * 8);
+  w.sort.hist = (int*)take(ss_sort_hist_entries(n) * 4);
+  w.sort.offs = (long long*)take(ss_sort_offs_entries(n) * 8);
+  w.sort.sums = (long long*)take(ss_sort_sums_entries(n) * 8);
   w.octree_bytes = kamd_spc_octree_workspace(n, level);
   w.octree = (void*)take(w.octree_bytes);
   w.total_bytes = (size_t)(p - (char*)base);
@@ -123,10 +123,9 @@ PcWs pc_ws(void* base, int64_t n, int level) {
 // after the keys: sort, run starts, octree (the one host read)
 int pc_build_tail(hipStream_t st, int64_t n, int level, const PcWs& w, int64_t* host_sizes) {
   KAMD_CHECK(hipGetLastError());
-  KAMD_CHECK(spc_sort_pairs(st, n, 3 * level, w.k0, w.v0, w.kt, w.vt, w.ks, w.vs, w.sort));
+  KAMD_CHECK(ss_sort(st, n, ss_passes_low(3 * level), w.k0, w.v0, w.kt, w.vt, w.ks, w.vs, w.sort));
   const unsigned g = (unsigned)kamd_cdiv(n, 256);
-  hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)nullptr, (const int64_t*)w.ks, 0, w.flag);
-  KAMD_CHECK(ms_scan(st, n, nullptr, w.flag, w.pos, w.sums));
+  KAMD_CHECK(ss_heads_scan(st, n, (const int64_t*)nullptr, w.ks, 0, w.flag, w.pos, w.sums));
   hipLaunchKernelGGL(pc_starts_kernel, dim3(g), dim3(256), 0, st, n, (const int*)w.flag, (const int64_t*)w.pos, w.starts);
   KAMD_CHECK(hipGetLastError());
   // sorted = 1 skips the build's sort only: its head / scan / unique pass keeps one code per run of equal codes

@@ -10,7 +10,7 @@
 //     item's levels through the sums on the device, a rebase that restarts the sums at every item, and one read of the pyramids;
 //   * generate_points: one launch per level for the whole batch (grid.y = item), children written as int16 `2 * parent + bit`
 //     straight from the parent's point -- no Morton array, no host read (the sizes are in the CPU pyramid);
-//   * build: codes masked to 3 * level bits, the keys-only radix sort of tet_sort.h, run heads / parents / gather of spc_octree.h
+//   * build: codes masked to 3 * level bits, the keys-only radix sort and run heads of sort_scan.h, parents / gather of spc_octree.h
 //     (shared with mesh_to_spc.hip); all levels on the device, one read of the level sizes;
 //   * query: one thread per query walks `level` dependent (byte, int) loads -- latency-bound by construction, nothing to tile;
 //   * to_dense: zero fill + one thread per (point, channel); the points of a level are distinct, so plain stores.
@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include "common.h"
-#include "tet_sort.h"
+#include "sort_scan.h"
 #include "spc_octree.h"
 #include "../../include/kaolin_amd.h"
 
@@ -27,7 +27,6 @@ namespace {
 constexpr int SP_MAX_LEVEL = 15;          // KAOLIN_SPC_MAX_LEVELS (spc_math.h:38)
 constexpr int SP_PYR = SP_MAX_LEVEL + 2;  // columns of a full pyramid row
 constexpr int SP_PYR_ITEM = 2 * SP_PYR + 1;  // ints per item read back: the (2, 17) pyramid, then the depth
-constexpr int SP_SCAN_BLOCK = 1024;
 
 inline unsigned sp_grid(int64_t items) {  // grid-stride kernels of 256 threads
   int64_t g = items > 0 ? (items + 255) / 256 : 1;
@@ -74,15 +73,13 @@ __global__ __launch_bounds__(256) void sp_unique_kernel(int64_t n, const int64_t
   if (i == 0) sizes[0] = pos[n];
 }
 // workspace of kamd_spc_octree_build for n codes at `level` (8-byte words unless noted):
-//   sizes (16) | codes A (n) | codes B (n) | pos (n + 1) | scan sums (n / 1024 + 2) | flag (n ints) | level bytes (level * n)
-//   | the sort's (digit, block) counts (256 * blocks ints), their offsets (256 * blocks + 1) and scan sums
+//   sizes (16) | codes A (n) | codes B (n) | pos (n + 1) | scan sums | flag (n ints) | level bytes (level * n)
+//   | the sort's scratch (sort_scan_host.h): (digit, block) counts (ints), their offsets and scan sums
 struct SpWs {
   int64_t *sizes, *ka, *kb, *pos, *sums;
   int* flag;
   unsigned char* level_bytes;
-  int* sort_hist;
-  long long *sort_offs, *sort_sums;
-  long long sort_blocks;
+  SsSortWs sort;
   size_t total_bytes;
 };
 SpWs sp_ws(void* base, int64_t n, int level) {
@@ -98,43 +95,19 @@ SpWs sp_ws(void* base, int64_t n, int level) {
   w.ka = (int64_t*)take(nn * 8);
   w.kb = (int64_t*)take(nn * 8);
   w.pos = (int64_t*)take(nn * 8 + 8);
-  w.sums = (int64_t*)take((nn / 1024 + 2) * 8);
+  w.sums = (int64_t*)take(ss_scan_sums_entries((long long)nn) * 8);
   w.flag = (int*)take(nn * 4);
   w.level_bytes = (unsigned char*)take((size_t)(level > 0 ? level : 1) * nn);
-  w.sort_blocks = mt_cdiv((long long)nn, MT_SORT_BLOCK);
-  const size_t hn = (size_t)256 * (size_t)w.sort_blocks;
-  w.sort_hist = (int*)take(hn * 4);
-  w.sort_offs = (long long*)take((hn + 1) * 8);
-  w.sort_sums = (long long*)take((hn / 1024 + 2) * 8);
+  w.sort.hist = (int*)take(ss_sort_hist_entries(n) * 4);
+  w.sort.offs = (long long*)take(ss_sort_offs_entries(n) * 8);
+  w.sort.sums = (long long*)take(ss_sort_sums_entries(n) * 8);
   w.total_bytes = (size_t)(p - (char*)base);
   return w;
 }
 
 // ---- scan ---------------------------------------------------------------------------------------------------------------------------
-// the bit counts of all bytes of the batch, summed inclusively over the WHOLE batch (G); the pyramid kernel and the rebase make
-// them per item.  total * 8 < 2^31 (checked by the caller), so an int holds every sum.
-__global__ __launch_bounds__(SP_SCAN_BLOCK) void sp_popc_sums_kernel(int64_t total, const unsigned char* __restrict__ octrees,
-                                                                    int64_t* __restrict__ sums) {
-  __shared__ long long s_wave[16];
-  const int64_t i = (int64_t)blockIdx.x * SP_SCAN_BLOCK + threadIdx.x;
-  const long long tot = ms_block_inclusive(i < total ? __popc((unsigned)octrees[i]) : 0, s_wave);
-  if (threadIdx.x == SP_SCAN_BLOCK - 1) sums[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(SP_SCAN_BLOCK) void sp_popc_apply_kernel(int64_t total, const unsigned char* __restrict__ octrees,
-                                                                     const int64_t* __restrict__ sums, int* __restrict__ g) {
-  __shared__ long long s_wave[16];
-  __shared__ long long s_off;
-  long long part = 0;  // the second level: the sums of the blocks before this one
-  for (int k = threadIdx.x; k < (int)blockIdx.x; k += SP_SCAN_BLOCK) part += sums[k];
-  const long long before = ms_block_inclusive(part, s_wave);
-  if (threadIdx.x == SP_SCAN_BLOCK - 1) s_off = before;
-  __syncthreads();
-  const long long off = s_off;
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * SP_SCAN_BLOCK + threadIdx.x;
-  const long long inc = ms_block_inclusive(i < total ? __popc((unsigned)octrees[i]) : 0, s_wave);
-  if (i < total) g[i] = (int)(off + inc);
-}
+// the bit counts of all bytes of the batch are summed inclusively over the WHOLE batch (ss_scan_inclusive of bytes); the pyramid
+// kernel and the rebase make them per item.  total * 8 < 2^31 (checked by the caller), so an int holds every sum.
 // one thread per item: scan_octrees.cu:80-96 on the device.  Level L holds g[first byte of level L - 1 ... ] so the item's sums are
 // read at `prev`, the number of points above level L; the index is clamped to the item's last byte.
 __global__ __launch_bounds__(256) void sp_pyramid_kernel(int64_t B, int64_t total, const int64_t* __restrict__ starts,
@@ -380,22 +353,12 @@ int kamd_spc_octree_build(void* stream, int64_t n, int level, const int64_t* mor
   int64_t* cur = w.ka;
   int64_t* nxt = w.kb;
   if (!sorted) {
-    const int passes = (3 * level + 7) / 8;
-    const long long nblk = w.sort_blocks;
-    for (int k = 0; k < passes; ++k) {
-      hipLaunchKernelGGL(mt_sort_hist_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (long long)n, (const unsigned long long*)cur,
-                         8 * k, nblk, w.sort_hist);
-      KAMD_CHECK(mt_scan(st, 256 * nblk, w.sort_hist, w.sort_offs, w.sort_sums));
-      hipLaunchKernelGGL(mt_sort_scatter_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (long long)n, (const unsigned long long*)cur,
-                         8 * k, nblk, (const long long*)w.sort_offs, (unsigned long long*)nxt);
-      int64_t* t = cur;
-      cur = nxt;
-      nxt = t;
-    }
+    const SsPasses passes = ss_passes_low(3 * level);
+    if (passes.count & 1) cur = w.kb, nxt = w.ka;  // where the last of an odd number of passes leaves the codes of A
+    KAMD_CHECK(ss_sort(st, n, passes, w.ka, nxt, cur, w.sort));
   }
   // one code per run of equal codes (with `sorted` the input is unique already: every code is a head)
-  hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)nullptr, (const int64_t*)cur, 0, w.flag);
-  KAMD_CHECK(ms_scan(st, n, nullptr, w.flag, w.pos, w.sums));
+  KAMD_CHECK(ss_heads_scan(st, n, (const int64_t*)nullptr, cur, 0, w.flag, w.pos, w.sums));
   hipLaunchKernelGGL(sp_unique_kernel, dim3(g), dim3(256), 0, st, n, (const int64_t*)cur, (const int*)w.flag, (const int64_t*)w.pos,
                      nxt, w.sizes);
   {
@@ -406,8 +369,7 @@ int kamd_spc_octree_build(void* stream, int64_t n, int level, const int64_t* mor
   // level l - 1 from the codes of level l; the counts stay on the device (grids sized by the bound n)
   for (int l = level; l > 0; --l) {
     const int64_t* n_ptr = (l == level) ? w.sizes : w.sizes + 1 + l;
-    hipLaunchKernelGGL(ms_heads_kernel, dim3(g), dim3(256), 0, st, (int64_t)0, n_ptr, (const int64_t*)cur, 3, w.flag);
-    KAMD_CHECK(ms_scan(st, n, n_ptr, w.flag, w.pos, w.sums));
+    KAMD_CHECK(ss_heads_scan(st, n, n_ptr, cur, 3, w.flag, w.pos, w.sums));
     hipLaunchKernelGGL(ms_parents_kernel, dim3(g), dim3(256), 0, st, n_ptr, (const int64_t*)cur, (const int*)w.flag,
                        (const int64_t*)w.pos, nxt, w.level_bytes + (size_t)(l - 1) * (size_t)n, w.sizes + 1 + (l - 1));
     int64_t* t = cur;
@@ -434,7 +396,7 @@ int kamd_spc_octree_gather(void* stream, int64_t n, int level, const void* works
 size_t kamd_spc_scan_workspace(int64_t total_bytes, int64_t B) {
   if (total_bytes <= 0 || B <= 0) return 0;
   auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return pad(((size_t)total_bytes / SP_SCAN_BLOCK + 2) * 8) + pad((size_t)B * SP_PYR_ITEM * 4) + pad((size_t)B * 4);
+  return pad(ss_scan_sums_entries(total_bytes) * 8) + pad((size_t)B * SP_PYR_ITEM * 4) + pad((size_t)B * 4);
 }
 
 int kamd_spc_scan_octrees(void* stream, int64_t total_bytes, int64_t B, const uint8_t* octrees, const int64_t* starts,
@@ -445,13 +407,11 @@ int kamd_spc_scan_octrees(void* stream, int64_t total_bytes, int64_t B, const ui
   auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   char* p = (char*)workspace;
   int64_t* sums = (int64_t*)p;
-  p += pad(((size_t)total_bytes / SP_SCAN_BLOCK + 2) * 8);
+  p += pad(ss_scan_sums_entries(total_bytes) * 8);
   int* pyr = (int*)p;
   p += pad((size_t)B * SP_PYR_ITEM * 4);
   int* base = (int*)p;
-  const unsigned nb = (unsigned)kamd_cdiv(total_bytes, SP_SCAN_BLOCK);
-  hipLaunchKernelGGL(sp_popc_sums_kernel, dim3(nb), dim3(SP_SCAN_BLOCK), 0, st, total_bytes, octrees, sums);
-  hipLaunchKernelGGL(sp_popc_apply_kernel, dim3(nb), dim3(SP_SCAN_BLOCK), 0, st, total_bytes, octrees, (const int64_t*)sums, exsum);
+  KAMD_CHECK(ss_scan_inclusive(st, total_bytes, octrees, exsum, sums));
   hipLaunchKernelGGL(sp_pyramid_kernel, dim3((unsigned)kamd_cdiv(B, 256)), dim3(256), 0, st, B, total_bytes, starts,
                      (const int*)exsum, pyr, base);
   hipLaunchKernelGGL(sp_rebase_kernel, dim3(sp_grid(total_bytes)), dim3(256), 0, st, total_bytes, B, starts, (const int*)base, exsum);

@@ -12,6 +12,7 @@
 #include <hip/hip_fp16.h>
 #include <float.h>
 #include "common.h"
+#include "sort_scan.h"
 #include "spc_octree.h"
 #include "../../include/kaolin_amd.h"
 
@@ -250,34 +251,6 @@ __global__ __launch_bounds__(256) void bf_colors_final_kernel(int64_t n, const i
   }
   reinterpret_cast<uchar4*>(colors)[i] = col;
   normals[3 * i] = nx, normals[3 * i + 1] = ny, normals[3 * i + 2] = nz;
-}
-
-// ---- inclusive sum of int32 (the block scan of spc_octree.h, two levels) ------------------------------------------------------------------
-// In = int: the values themselves; In = unsigned char: the bit counts of the bytes (the exsum of an octree)
-__device__ __forceinline__ long long bf_scan_value(const int* in, int64_t i) { return in[i]; }
-__device__ __forceinline__ long long bf_scan_value(const unsigned char* in, int64_t i) { return __popc((unsigned)in[i]); }
-template <typename In>
-__global__ __launch_bounds__(1024) void bf_scan_sums_kernel(int64_t n, const In* __restrict__ in, int64_t* __restrict__ sums) {
-  __shared__ long long s_wave[16];
-  const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-  const long long tot = ms_block_inclusive(i < n ? bf_scan_value(in, i) : 0, s_wave);
-  if (threadIdx.x == 1023) sums[blockIdx.x] = tot;
-}
-template <typename In>
-__global__ __launch_bounds__(1024) void bf_scan_apply_kernel(int64_t n, const In* __restrict__ in, const int64_t* __restrict__ sums,
-                                                             int* __restrict__ out) {
-  __shared__ long long s_wave[16];
-  __shared__ long long s_off;
-  long long part = 0;
-  for (int k = threadIdx.x; k < (int)blockIdx.x; k += 1024) part += sums[k];
-  const long long before = ms_block_inclusive(part, s_wave);
-  if (threadIdx.x == 1023) s_off = before;
-  __syncthreads();
-  const long long off = s_off;
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-  const long long inc = ms_block_inclusive(i < n ? bf_scan_value(in, i) : 0, s_wave);
-  if (i < n) out[i] = (int)(off + inc);
 }
 
 // ---- subdivide / compactify ---------------------------------------------------------------------------------------------------------------
@@ -580,16 +553,12 @@ int kamd_spc_bf_colors_final(void* stream, int64_t n, const int16_t* points, con
   KAMD_RETURN_LAST_ERROR();
 }
 
-size_t kamd_spc_bf_scan_workspace(int64_t n) { return n > 0 ? ((size_t)n / 1024 + 2) * 8 : 0; }
+size_t kamd_spc_bf_scan_workspace(int64_t n) { return n > 0 ? ss_scan_sums_entries(n) * 8 : 0; }
 
 int kamd_spc_bf_inclusive_sum(void* stream, int64_t n, const int32_t* in, int32_t* out, void* workspace) {
   if (n <= 0) return 0;
   if (workspace == nullptr) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned nb = (unsigned)((n + 1023) / 1024);
-  hipLaunchKernelGGL(bf_scan_sums_kernel<int>, dim3(nb), dim3(1024), 0, st, n, in, (int64_t*)workspace);
-  hipLaunchKernelGGL(bf_scan_apply_kernel<int>, dim3(nb), dim3(1024), 0, st, n, in, (const int64_t*)workspace, out);
-  KAMD_RETURN_LAST_ERROR();
+  return ss_scan_inclusive((hipStream_t)stream, n, in, out, (int64_t*)workspace);
 }
 
 int kamd_spc_bf_subdivide(void* stream, int64_t n, int64_t pass, const int16_t* points, const int32_t* insum, int16_t* new_points,
@@ -676,7 +645,7 @@ static BfCellsWs bf_cells_ws(void* base, int64_t num_bytes) {
   };
   const size_t nn = (size_t)(num_bytes > 0 ? num_bytes : 1);
   w.hdr = (int64_t*)take(BF_HDR * 8);
-  w.sums = (int64_t*)take((nn / 1024 + 2) * 8);
+  w.sums = (int64_t*)take(ss_scan_sums_entries((long long)nn) * 8);
   w.exsum = (int*)take(nn * 4);
   w.sub = (int64_t*)take(nn * 8);
   w.total_bytes = (size_t)(p - (char*)base);
@@ -692,9 +661,7 @@ int kamd_spc_bf_cells_count(void* stream, int64_t num_bytes, int level, const ui
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const BfCellsWs w = bf_cells_ws(workspace, num_bytes);
-  const unsigned nb = (unsigned)((num_bytes + 1023) / 1024);
-  hipLaunchKernelGGL(bf_scan_sums_kernel<unsigned char>, dim3(nb), dim3(1024), 0, st, num_bytes, octree, w.sums);
-  hipLaunchKernelGGL(bf_scan_apply_kernel<unsigned char>, dim3(nb), dim3(1024), 0, st, num_bytes, octree, (const int64_t*)w.sums, w.exsum);
+  KAMD_CHECK(ss_scan_inclusive(st, num_bytes, octree, w.exsum, w.sums));
   hipLaunchKernelGGL(bf_cells_levels_kernel, dim3(1), dim3(64), 0, st, level, num_bytes, (const int*)w.exsum, w.hdr);
   unsigned g = bf_blocks(num_bytes);
   if (g > KAMD_NUM_CU * 16u) g = KAMD_NUM_CU * 16u;

@@ -1,7 +1,6 @@
-// The octree kernels that the two SPC builders share (mesh_to_spc.hip, spc.hip): the Morton layout, an exclusive scan of ints
-// into int64 offsets whose length may live on the device, the heads of runs of equal (shifted) Morton codes, the parents of a
-// level (code + children bitmap) and the gather of the levels into one octree.  Every name lives in an unnamed namespace: each
-// translation unit gets its own copy.
+// The octree kernels that the two SPC builders share (mesh_to_spc.hip, spc.hip): the Morton layout, the parents of a level (code +
+// children bitmap, from the run heads and scan of sort_scan.h) and the gather of the levels into one octree.  Every name lives
+// in an unnamed namespace: each translation unit gets its own copy.
 #pragma once
 #include "common.h"
 
@@ -35,57 +34,6 @@ __device__ __forceinline__ void ms_to_point(uint64_t m, int* x, int* y, int* z) 
   *z = ms_compact3(m);
 }
 
-// ---- exclusive scan of n ints into n + 1 int64 offsets (offsets[n] = total): sums of 1024-blocks, then apply ----------
-__device__ __forceinline__ long long ms_block_inclusive(long long v, long long* s_wave) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  long long woff = 0;
-  for (int k = 0; k < wave; ++k) woff += s_wave[k];
-  return woff + inc;
-}
-// n may live on the device (n_ptr != nullptr): entries at or beyond it count as 0
-__global__ __launch_bounds__(1024) void ms_scan_sums_kernel(int64_t n_host, const int64_t* __restrict__ n_ptr,
-                                                            const int* __restrict__ in, int64_t* __restrict__ sums) {
-  __shared__ long long s_wave[16];
-  const int64_t n = n_ptr ? *n_ptr : n_host;
-  const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-  const long long tot = ms_block_inclusive(i < n ? in[i] : 0, s_wave);
-  if (threadIdx.x == 1023) sums[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(1024) void ms_scan_apply_kernel(int64_t n_host, const int64_t* __restrict__ n_ptr,
-                                                             const int* __restrict__ in, const int64_t* __restrict__ sums,
-                                                             int64_t* __restrict__ out) {
-  __shared__ long long s_wave[16];
-  __shared__ long long s_off;
-  const int64_t n = n_ptr ? *n_ptr : n_host;
-  long long part = 0;
-  for (int k = threadIdx.x; k < (int)blockIdx.x; k += 1024) part += sums[k];
-  const long long before = ms_block_inclusive(part, s_wave);
-  if (threadIdx.x == 1023) s_off = before;
-  __syncthreads();
-  const long long off = s_off;
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-  const long long v = i < n ? in[i] : 0;
-  const long long inc = ms_block_inclusive(v, s_wave);
-  if (i < n) out[i] = off + inc - v;
-  if (i == n - 1) out[n] = off + inc;
-  if (n == 0 && i == 0) out[0] = 0;
-}
-int ms_scan(hipStream_t st, int64_t n_bound, const int64_t* n_ptr, const int* in, int64_t* out, int64_t* sums) {
-  const unsigned nb = (unsigned)(n_bound > 0 ? (n_bound + 1023) / 1024 : 1);
-  hipLaunchKernelGGL(ms_scan_sums_kernel, dim3(nb), dim3(1024), 0, st, n_bound, n_ptr, in, sums);
-  hipLaunchKernelGGL(ms_scan_apply_kernel, dim3(nb), dim3(1024), 0, st, n_bound, n_ptr, in, sums, out);
-  return (int)hipGetLastError();
-}
-
 __global__ __launch_bounds__(256) void ms_copy_words_kernel(int64_t n, const int64_t* __restrict__ a, int64_t* __restrict__ a_out,
                                                             const int64_t* __restrict__ b, int64_t* __restrict__ b_out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -96,13 +44,6 @@ __global__ __launch_bounds__(256) void ms_copy_words_kernel(int64_t n, const int
 
 // ---- after the sort: one voxel per run of equal Morton codes, then the octree bottom-up --------------------------------
 // sizes[0] = voxels, sizes[1 + l] = nodes of octree level l (root = level 0)
-__global__ __launch_bounds__(256) void ms_heads_kernel(int64_t n_host, const int64_t* __restrict__ n_ptr,
-                                                       const int64_t* __restrict__ m, int shift, int* __restrict__ flag) {
-  const int64_t n = n_ptr ? *n_ptr : n_host;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) flag[i] = (i == 0 || ((uint64_t)m[i - 1] >> shift) != ((uint64_t)m[i] >> shift)) ? 1 : 0;
-}
-
 // nodes of the level above: parent code + children bitmap of every run of siblings (spc_cuda.cu:64-90)
 __global__ __launch_bounds__(256) void ms_parents_kernel(const int64_t* __restrict__ n_ptr, const int64_t* __restrict__ m,
                                                          const int* __restrict__ flag, const int64_t* __restrict__ pos,

@@ -3,7 +3,7 @@
 // Replaces kaolin/csrc/render/spc/raytrace_cuda.cu:64-269 + :504-626 (decide / scan / subdivide per level, the (ray, node) list written
 // and re-read at every level, one blocking read per level) with spc_render_utils.cuh:21-143 (the box test), and :327-502 + :680-802
 // (one thread per pack over a `nonzero` index list, channels serially; float atomics in sum_reduce).  Here:
-//   * ray tracing: one thread per ray walks its subtree depth-first, twice -- a count launch, the exclusive scan of tet_sort.h
+//   * ray tracing: one thread per ray walks its subtree depth-first, twice -- a count launch, the exclusive scan of sort_scan.h
 //     (ints -> N + 1 int64 offsets, total in the last slot), ONE host read of the total, an emit launch that repeats the walk and
 //     writes at the ray's offset.  4 launches whatever `level` is; no (ray, node) pair ever touches memory.  The depth-first
 //     sequence of a ray is the sequence the reference's level-by-level expansion produces for it, and rays come out in input order.
@@ -16,7 +16,7 @@
 // Every data-derived index is compared with the size of the buffer it indexes before use (the list is in DESIGN.md).
 #include <hip/hip_runtime.h>
 #include "common.h"
-#include "tet_sort.h"
+#include "sort_scan.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_walk_kernel(int64_t N, int level,
   if (!EMIT) counts[i] = n;
 }
 
-// workspace of a trace of N rays: counts (N ints) | offsets (N + 1 int64) | scan sums (N / 1024 + 2 int64)
+// workspace of a trace of N rays: counts (N ints) | offsets (N + 1 int64) | scan sums (int64)
 struct RtWs {
   int* counts;
   long long *offs, *sums;
@@ -173,7 +173,7 @@ RtWs rt_ws(void* base, int64_t N) {
   const size_t nn = (size_t)(N > 0 ? N : 1);
   w.counts = (int*)take(nn * 4);
   w.offs = (long long*)take((nn + 1) * 8);
-  w.sums = (long long*)take((nn / 1024 + 2) * 8);
+  w.sums = (long long*)take(ss_scan_sums_entries((long long)nn) * 8);
   w.total_bytes = (size_t)(p - (char*)base);
   return w;
 }
@@ -294,7 +294,7 @@ int kamd_spc_raytrace_count(void* stream, int64_t N, int level, int64_t num_byte
                        exsum, points, origin, direction, w.counts, (const long long*)nullptr, (int64_t)0, (int*)nullptr,
                        (float*)nullptr);
   KAMD_CHECK(hipGetLastError());
-  KAMD_CHECK(mt_scan(st, N, w.counts, w.offs, w.sums));
+  KAMD_CHECK(ss_scan(st, N, (const long long*)nullptr, w.counts, w.offs, w.sums));
   // the one host read of a trace: the number of hits sizes the results
   long long total = 0;
   KAMD_CHECK(hipMemcpyAsync(&total, w.offs + N, sizeof(long long), hipMemcpyDeviceToHost, st));

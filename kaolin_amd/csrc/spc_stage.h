@@ -1,4 +1,4 @@
-// The stage walker and the stable pair sort of the SPC voxelizers, with the primitive's voxel test as a template parameter.
+// The stage walker of the SPC voxelizers, with the primitive's voxel test as a template parameter.
 // Lifted out of mesh_to_spc.hip (launch shapes and every test's arithmetic unchanged: tests/test_mesh_to_spc.py is the guard) and
 // shared with gs_to_spc.hip.
 // Every name lives in an unnamed namespace: each translation unit gets its own copy.
@@ -103,107 +103,6 @@ __global__ __launch_bounds__(256) void spc_stage_kernel(int64_t n, PRIM prim, co
     }
   }
   if (!EMIT && i < n && k == 0) counts[i] = count;
-}
-
-// ---- stable LSD radix sort of (Morton code, primitive) pairs by code, 8 bits a pass ---------------------------------------------
-// Per pass a digit histogram per block of 2 048 pairs, ONE exclusive scan over the (digit, block) counts (ms_scan) and a scatter
-// that ranks the pairs of a block in their original order (wavefront by wavefront: the lanes sharing a digit are found with eight
-// ballots, lower lanes first; wavefronts and rounds of 256 in order through LDS counters), so equal codes keep their order.  Every
-// destination is a prefix sum of the histogram of the same n keys, so it lies in [0, n).
-constexpr int SPC_SORT_ITEMS = 8, SPC_SORT_BLOCK = 256 * SPC_SORT_ITEMS;
-__global__ __launch_bounds__(256) void spc_sort_hist_kernel(int64_t n, const uint64_t* __restrict__ keys, int shift, int nblk,
-                                                            int* __restrict__ hist) {
-  __shared__ int s_h[256];
-  s_h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * SPC_SORT_BLOCK;
-#pragma unroll
-  for (int r = 0; r < SPC_SORT_ITEMS; ++r) {
-    const int64_t e = base + r * 256 + threadIdx.x;
-    if (e < n) atomicAdd(&s_h[(int)((keys[e] >> shift) & 255u)], 1);
-  }
-  __syncthreads();
-  hist[(size_t)threadIdx.x * nblk + blockIdx.x] = s_h[threadIdx.x];
-}
-__global__ __launch_bounds__(256) void spc_sort_scatter_kernel(int64_t n, const uint64_t* __restrict__ keys,
-                                                               const int64_t* __restrict__ vals, int shift, int nblk,
-                                                               const int64_t* __restrict__ offs, uint64_t* __restrict__ keys_out,
-                                                               int64_t* __restrict__ vals_out) {
-  __shared__ long long s_run[256];
-  __shared__ int s_wc[4][256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  s_run[tid] = offs[(size_t)tid * nblk + blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) s_wc[w][tid] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * SPC_SORT_BLOCK;
-  for (int r = 0; r < SPC_SORT_ITEMS; ++r) {
-    const int64_t e = base + r * 256 + tid;
-    const bool on = e < n;
-    const uint64_t key = on ? keys[e] : 0ull;
-    const int64_t val = on ? vals[e] : 0;
-    const int digit = (int)((key >> shift) & 255u);
-    // the lanes of this wavefront that hold the same digit (and a pair at all)
-    unsigned long long peers = __ballot(on);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const unsigned long long m = __ballot((digit >> bit) & 1);
-      peers &= ((digit >> bit) & 1) ? m : ~m;
-    }
-    const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-    if (on && rank == 0) s_wc[wave][digit] = __popcll(peers);
-    __syncthreads();
-    if (on) {
-      long long pos = s_run[digit] + rank;
-      for (int w = 0; w < wave; ++w) pos += s_wc[w][digit];
-      if (pos >= 0 && pos < n) {
-        keys_out[pos] = key;
-        vals_out[pos] = val;
-      }
-    }
-    __syncthreads();
-    s_run[tid] += (s_wc[0][tid] + s_wc[1][tid]) + (s_wc[2][tid] + s_wc[3][tid]);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) s_wc[w][tid] = 0;
-    __syncthreads();
-  }
-}
-inline int spc_sort_blocks(int64_t n) { return (int)(((n > 0 ? n : 1) + SPC_SORT_BLOCK - 1) / SPC_SORT_BLOCK); }
-
-// the sort's scratch for n pairs: (digit, block) counts (ints), their offsets (+ 1) and the scan's block sums
-struct SpcSortWs {
-  int* hist;
-  int64_t *offs, *sums;
-};
-inline size_t spc_sort_hist_entries(int64_t n) { return (size_t)256 * (size_t)spc_sort_blocks(n); }
-
-// n pairs (keys_in, vals_in) -> sorted by the low `bits` key bits, stable, into (keys_dst, vals_dst); (keys_tmp, vals_tmp) is the
-// other side of the ping-pong.  The inputs are only read.  bits == 0: a copy.
-inline int spc_sort_pairs(hipStream_t st, int64_t n, int bits, const uint64_t* keys_in, const int64_t* vals_in, uint64_t* keys_tmp,
-                          int64_t* vals_tmp, uint64_t* keys_dst, int64_t* vals_dst, const SpcSortWs& w) {
-  const int passes = (bits + 7) / 8;
-  const int nblk = spc_sort_blocks(n);
-  if (passes == 0) {
-    unsigned cg = (unsigned)kamd_cdiv(n, 256);
-    if (cg > (unsigned)KAMD_NUM_CU * 8u) cg = (unsigned)KAMD_NUM_CU * 8u;
-    hipLaunchKernelGGL(ms_copy_words_kernel, dim3(cg), dim3(256), 0, st, n, (const int64_t*)keys_in, (int64_t*)keys_dst, vals_in,
-                       vals_dst);
-    return (int)hipGetLastError();
-  }
-  const uint64_t* src_k = keys_in;
-  const int64_t* src_v = vals_in;
-  for (int k = 0; k < passes; ++k) {  // the last pass lands in dst
-    const bool to_dst = ((passes - 1 - k) & 1) == 0;
-    uint64_t* dst_k = to_dst ? keys_dst : keys_tmp;
-    int64_t* dst_v = to_dst ? vals_dst : vals_tmp;
-    hipLaunchKernelGGL(spc_sort_hist_kernel, dim3(nblk), dim3(256), 0, st, n, src_k, 8 * k, nblk, w.hist);
-    KAMD_CHECK(ms_scan(st, (int64_t)256 * nblk, nullptr, w.hist, w.offs, w.sums));
-    hipLaunchKernelGGL(spc_sort_scatter_kernel, dim3(nblk), dim3(256), 0, st, n, src_k, src_v, 8 * k, nblk,
-                       (const int64_t*)w.offs, dst_k, dst_v);
-    src_k = dst_k;
-    src_v = dst_v;
-  }
-  return (int)hipGetLastError();
 }
 
 }  // namespace

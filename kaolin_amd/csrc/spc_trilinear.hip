@@ -5,7 +5,7 @@
 // dictionaries of Morton codes), kaolin/ops/spc/points.py:172-341 (the interpolation's backward: a chain of torch operators) and
 // kaolin/csrc/ops/spc/point_utils_cuda.cu:44-124 (the forward: one thread per sample looping over the feature dimension).  Here:
 //   * make_dual: ALL levels in one pass -- one key `level << 48 | Morton(corner)` per (point, corner), the keys-only radix sort of
-//     tet_sort.h over the 3 (max_level + 1) code bits and then the level bits, heads / scan, the level starts found by max_level + 2
+//     sort_scan.h over the 3 (max_level + 1) code bits and then the level bits, heads / scan, the level starts found by max_level + 2
 //     binary searches on the device, ONE host read of them; a second entry point decodes the run heads to int16 rows;
 //   * make_trinkets: one launch, a thread per (point, corner) searches the corner's code in its level's sorted dual range; the
 //     thread of corner 0 also searches the parent `point >> 1` in the previous primary level.  Not found -> -1, never a read
@@ -22,14 +22,13 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include "common.h"
-#include "tet_sort.h"
+#include "sort_scan.h"
 #include "spc_octree.h"
 #include "spc_dual_host.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
 
-static_assert(SD_SORT_BLOCK == MT_SORT_BLOCK, "spc_dual_host.h sizes the histogram of tet_sort.h's sort");
 constexpr unsigned long long SD_CODE_MASK = (1ull << SD_LEVEL_SHIFT) - 1ull;
 
 inline unsigned sd_grid(int64_t items) {  // grid-stride kernels of 256 threads
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(64) void sd_level_starts_kernel(long long nk, int m
   const int l = threadIdx.x;
   if (l > max_level + 1) return;
   long long lo = nk;
-  if (l <= max_level) lo = mt_rank(keys, nk, (unsigned long long)l << SD_LEVEL_SHIFT);  // in [0, nk]
+  if (l <= max_level) lo = ss_rank(keys, nk, (unsigned long long)l << SD_LEVEL_SHIFT);  // in [0, nk]
   starts[l] = pos[lo];  // pos has nk + 1 entries
 }
 __global__ __launch_bounds__(256) void sd_decode_kernel(long long nk, long long num_dual, const unsigned long long* __restrict__ keys,
@@ -455,24 +454,13 @@ int kamd_spc_dual_build(void* stream, int64_t num_points, int max_level, const i
   if (workspace_bytes < lay.bytes) return (int)hipErrorInvalidValue;
   const SdWs w = sd_ws(workspace, lay);
   hipStream_t st = (hipStream_t)stream;
-  const long long nk = lay.keys, nblk = lay.nsb;
+  const long long nk = lay.keys;
   hipLaunchKernelGGL(sd_corner_keys_kernel, dim3(sd_grid(nk)), dim3(256), 0, st, (long long)num_points, lv, points, w.ka);
-  unsigned long long *cur = w.ka, *nxt = w.kb;
-  const int passes = sd_code_passes(max_level) + sd_level_passes(max_level);
-  for (int k = 0; k < passes; ++k) {
-    const int shift = sd_pass_shift(max_level, k);
-    hipLaunchKernelGGL(mt_sort_hist_kernel, dim3((unsigned)nblk), dim3(256), 0, st, nk, (const unsigned long long*)cur, shift, nblk,
-                       w.hist);
-    KAMD_CHECK(mt_scan(st, 256 * nblk, w.hist, w.hoffs, w.sums));
-    hipLaunchKernelGGL(mt_sort_scatter_kernel, dim3((unsigned)nblk), dim3(256), 0, st, nk, (const unsigned long long*)cur, shift, nblk,
-                       (const long long*)w.hoffs, nxt);
-    unsigned long long* t = cur;
-    cur = nxt;
-    nxt = t;
-  }
-  hipLaunchKernelGGL(mt_heads_kernel, dim3(mt_grid(nk, 256)), dim3(256), 0, st, nk, (const unsigned long long*)cur, w.flags);
-  KAMD_CHECK(mt_scan(st, nk, w.flags, w.pos, w.sums));
-  hipLaunchKernelGGL(sd_level_starts_kernel, dim3(1), dim3(64), 0, st, nk, max_level, (const unsigned long long*)cur,
+  const bool in_b = sd_sorted_in_b(max_level);  // (kamd_spc_dual_emit looks there too)
+  unsigned long long* sorted = in_b ? w.kb : w.ka;
+  KAMD_CHECK(ss_sort(st, nk, sd_passes(max_level), w.ka, in_b ? w.ka : w.kb, sorted, ss_sort_ws(w.hist, w.hoffs, w.sums)));
+  KAMD_CHECK(ss_heads_scan(st, nk, (const long long*)nullptr, sorted, 0, w.flags, w.pos, w.sums));
+  hipLaunchKernelGGL(sd_level_starts_kernel, dim3(1), dim3(64), 0, st, nk, max_level, (const unsigned long long*)sorted,
                      (const long long*)w.pos, w.sizes);
   KAMD_CHECK(hipGetLastError());
   // the one host read of the call: the level starts size the result and are the dual pyramid

@@ -11,13 +11,13 @@
 // TOPOLOGY (once per call: it does not depend on the batch)
 //   1. st_keys_kernel     THE pass over `tets` (two 16-byte loads per tet): the six keys min << 32 | max of tet t at keys[6 t ..],
 //                         as three 16-byte stores.  Bound: 32 B read + 48 B written per tet.
-//   2. sort               tet_sort.h: stable 8-bit LSD radix sort of the keys alone, over the digits below ceil(log2 V) of either
+//   2. sort               sort_scan.h: stable 8-bit LSD radix sort of the keys alone, over the digits below ceil(log2 V) of either
 //                         half only (2 x ceil(bits / 8) passes; each reads the keys twice and scatters them once).  Most of the
 //                         topology's traffic: 6 passes x 6 T x 24 B at V = 2.1 M.
 //   3. heads / scan / unique   the first of every run of equal keys, compacted: the unique keys ARE the edge list.  The HOST reads
 //                         E -- the one stream synchronisation of the call.
 //   4. st_edges_kernel    unique keys -> edges (E, 2) int64, a 16-byte store per edge.
-//      st_emit_kernel     per tet: re-reads the tet, ranks its six keys by binary search in the unique keys (mt_rank: ~log2 E
+//      st_emit_kernel     per tet: re-reads the tet, ranks its six keys by binary search in the unique keys (ss_rank: ~log2 E
 //                         dependent loads, the top levels from L2) and writes its row of each of the eight blocks as two 16-byte
 //                         stores (256 B per tet; consecutive threads write consecutive rows of a block).  A permutation carried
 //                         through the sort would replace the searches by 6 T x 8 B more traffic in each of the passes and a
@@ -36,13 +36,12 @@
 //                                                  a transposed list, which would cost a second sort of E keys per topology.
 // Every kernel is a plain bounded launch; none waits on another workgroup.
 #include "common.h"
-#include "tet_sort.h"
+#include "sort_scan.h"
+#include "tet_load.h"
 #include "subdivide_tetmesh_host.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
-
-static_assert(ST_SORT_BLOCK == MT_SORT_BLOCK, "the workspace is laid out for the sort's block size");
 
 __device__ __forceinline__ unsigned long long st_key(unsigned long long p, unsigned long long q) {
   return p < q ? (p << 32) | q : (q << 32) | p;
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(256) void st_emit_kernel(const int64_t* __restrict_
   unsigned long long k[6], r[6];
   st_tet_keys(tet, k);
 #pragma unroll
-  for (int s = 0; s < 6; ++s) r[s] = V + (unsigned long long)mt_rank(uniq, E, k[s]);
+  for (int s = 0; s < 6; ++s) r[s] = V + (unsigned long long)ss_rank(uniq, E, k[s]);
   const unsigned long long a = tet.id[0], b = tet.id[1], c = tet.id[2], d = tet.id[3];
   const unsigned long long ab = r[0], ac = r[1], ad = r[2], bc = r[3], bd = r[4], cd = r[5];
   ulonglong2* out = (ulonglong2*)new_tets;  // row (block * T + t): 32 bytes, two 16-byte words
@@ -194,41 +193,14 @@ int st_edges(hipStream_t st, long long T, long long V, const int64_t* tets, void
   const StLayout l = st_layout(T);
   char* ws = (char*)workspace;
   unsigned long long* keys = (unsigned long long*)(ws + l.keys_a);
-  unsigned long long* other = (unsigned long long*)(ws + l.keys_b);
-  int* flags = (int*)(ws + l.flags);
-  long long* pos = (long long*)(ws + l.pos);
-  int* hist = (int*)(ws + l.hist);
-  long long* hoffs = (long long*)(ws + l.hoffs);
+  unsigned long long* uniq = (unsigned long long*)(ws + l.keys_b);
   long long* sums = (long long*)(ws + l.sums);
 
-  hipLaunchKernelGGL(st_keys_kernel, dim3(mt_grid(T, 256)), dim3(256), 0, st, tets, T, keys);
+  hipLaunchKernelGGL(st_keys_kernel, dim3(ss_grid(T, 256)), dim3(256), 0, st, tets, T, keys);
   KAMD_CHECK(hipGetLastError());
-  const int passes = st_passes_per_half(V);
-  for (int half = 0; half < 2; ++half) {
-    for (int pass = 0; pass < passes; ++pass) {
-      const int shift = 32 * half + 8 * pass;
-      hipLaunchKernelGGL(mt_sort_hist_kernel, dim3((unsigned)l.nsb), dim3(256), 0, st, l.n, (const unsigned long long*)keys, shift,
-                         l.nsb, hist);
-      KAMD_CHECK(mt_scan(st, l.nsb * 256, hist, hoffs, sums));
-      hipLaunchKernelGGL(mt_sort_scatter_kernel, dim3((unsigned)l.nsb), dim3(256), 0, st, l.n, (const unsigned long long*)keys,
-                         shift, l.nsb, (const long long*)hoffs, other);
-      unsigned long long* tmp = keys;
-      keys = other;
-      other = tmp;
-    }
-  }
-  KAMD_CHECK(hipGetLastError());
-  // (2 * passes swaps: `keys` is keys_a again, and keys_b is free for the unique keys)
-  hipLaunchKernelGGL(mt_heads_kernel, dim3(mt_grid(l.n, 256)), dim3(256), 0, st, l.n, (const unsigned long long*)keys, flags);
-  KAMD_CHECK(mt_scan(st, l.n, flags, pos, sums));
-  hipLaunchKernelGGL(mt_unique_kernel, dim3(mt_grid(l.n, 256)), dim3(256), 0, st, l.n, (const unsigned long long*)keys,
-                     (const int*)flags, (const long long*)pos, other);
-  KAMD_CHECK(hipGetLastError());
-  long long h = 0;
-  KAMD_CHECK(hipMemcpyAsync(&h, pos + l.n, 8, hipMemcpyDeviceToHost, st));
-  KAMD_CHECK(hipStreamSynchronize(st));
-  *host_num_edges = h;
-  return 0;
+  KAMD_CHECK(ss_sort(st, l.n, ss_passes_halves(st_id_bits(V)), keys, uniq, keys,  // in place, through keys_b
+                     ss_sort_ws((int*)(ws + l.hist), (long long*)(ws + l.hoffs), sums)));
+  return ss_unique(st, l.n, keys, (int*)(ws + l.flags), (long long*)(ws + l.pos), sums, uniq, host_num_edges);
 }
 
 int st_emit(hipStream_t st, long long T, long long V, const int64_t* tets, const void* workspace, long long E, int64_t* edges,
@@ -239,15 +211,15 @@ int st_emit(hipStream_t st, long long T, long long V, const int64_t* tets, const
       ((uintptr_t)edges & 15) != 0 || ((uintptr_t)new_tets & 15) != 0)
     return (int)hipErrorInvalidValue;
   const unsigned long long* uniq = (const unsigned long long*)((const char*)workspace + st_layout(T).keys_b);
-  hipLaunchKernelGGL(st_edges_kernel, dim3(mt_grid(E, 256)), dim3(256), 0, st, E, uniq, edges);
-  hipLaunchKernelGGL(st_emit_kernel, dim3(mt_grid(T, 256)), dim3(256), 0, st, tets, T, (unsigned long long)V, uniq, E, new_tets);
+  hipLaunchKernelGGL(st_edges_kernel, dim3(ss_grid(E, 256)), dim3(256), 0, st, E, uniq, edges);
+  hipLaunchKernelGGL(st_emit_kernel, dim3(ss_grid(T, 256)), dim3(256), 0, st, tets, T, (unsigned long long)V, uniq, E, new_tets);
   KAMD_RETURN_LAST_ERROR();
 }
 
 // blocks of 256 over `rows` rows of both tensors, or 0 when that many do not fit a launch
 inline long long st_blocks(long long rows, long long channels) {
   if (rows > (1ll << 40) / (channels > 0 ? channels : 1)) return 0;
-  const long long blocks = mt_cdiv(rows * channels, 256);
+  const long long blocks = ss_cdiv(rows * channels, 256);
   return blocks < (1ll << 31) ? blocks : 0;
 }
 inline bool st_bad_midpoint_extents(long long B, long long V, long long E, long long D) {

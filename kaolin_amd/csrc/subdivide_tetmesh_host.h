@@ -5,7 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-constexpr int ST_SORT_BLOCK = 2048;  // keys per workgroup of the radix sort (tet_sort.h MT_SORT_BLOCK)
+#include "sort_scan_host.h"
 
 // V < 2^32: an id is one half of a 64-bit key.  T <= 2^35: 6 T keys in workgroups of 256 stay below 2^31 workgroups.
 inline bool st_bad_extents(long long T, long long V) { return T < 0 || V < 0 || V >= (1ll << 32) || T > (1ll << 35); }
@@ -16,12 +16,11 @@ inline int st_id_bits(long long V) {
   while (nb < 32 && (1ll << nb) < V) ++nb;
   return nb;
 }
-// 8-bit passes over one half of the keys; the sort runs this many over the max half, then as many over the min half: an even
-// total, so the sorted keys end in the buffer they started in
-inline int st_passes_per_half(long long V) { return (st_id_bits(V) + 7) / 8; }
+// 8-bit passes over one half of the keys; the sort runs this many over the max half, then as many over the min half
+// (ss_passes_halves)
+inline int st_passes_per_half(long long V) { return ss_passes(st_id_bits(V)); }
 
 inline size_t st_align(size_t x) { return (x + 15) & ~(size_t)15; }
-inline long long st_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
 // keys_a: the 6 T keys, sorted in place (through keys_b); keys_b: after the sort, the unique keys.  flags / pos: heads of the
 // runs of equal keys and their exclusive scan (pos[n] = E).  hist / hoffs / sums: the sort's (digit, block) counts and the scans'
@@ -33,16 +32,15 @@ struct StLayout {
 inline StLayout st_layout(long long T) {
   StLayout l;
   l.n = 6 * T;
-  l.nsb = st_cdiv(l.n, ST_SORT_BLOCK);
-  const long long scan_max = l.nsb * 256 > l.n ? l.nsb * 256 : l.n;
+  l.nsb = ss_sort_blocks(l.n);
   size_t o = 0;
   l.keys_a = o, o += st_align((size_t)l.n * 8);
   l.keys_b = o, o += st_align((size_t)l.n * 8);
   l.flags = o, o += st_align((size_t)l.n * 4);
   l.pos = o, o += st_align(((size_t)l.n + 1) * 8);
-  l.hist = o, o += st_align((size_t)l.nsb * 256 * 4);
-  l.hoffs = o, o += st_align(((size_t)l.nsb * 256 + 1) * 8);
-  l.sums = o, o += st_align(((size_t)st_cdiv(scan_max, 1024) + 1) * 8);
+  l.hist = o, o += st_align(ss_sort_hist_entries(l.n) * 4);
+  l.hoffs = o, o += st_align(ss_sort_offs_entries(l.n) * 8);
+  l.sums = o, o += st_align(ss_sort_unique_sums_entries(l.n) * 8);
   l.bytes = o;
   return l;
 }

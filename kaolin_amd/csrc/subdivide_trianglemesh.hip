@@ -14,7 +14,7 @@
 //
 // TOPOLOGY (once per iteration: it does not depend on the batch)
 //   1. sl_keys_kernel     the three keys min << 32 | max of face f at keys[3 f ..].
-//   2. sort               tet_sort.h: stable 8-bit LSD radix sort of the keys alone, over the digits below ceil(log2 V) of either
+//   2. sort               sort_scan.h: stable 8-bit LSD radix sort of the keys alone, over the digits below ceil(log2 V) of either
 //                         half only.
 //   3. heads / scan / unique   the unique keys ARE the edge list.  The HOST reads E -- the one stream synchronisation.
 //   4. sl_edges_kernel    unique keys -> edges (E, 2) int64 and the swapped keys max << 32 | min.
@@ -33,13 +33,11 @@
 //             sl_backward_opp_kernel: the 1/8 terms of the opposite corners, one native fp atomic add per (edge, slot, channel).
 // Every kernel is a plain bounded launch; none waits on another workgroup.
 #include "common.h"
-#include "tet_sort.h"
+#include "sort_scan.h"
 #include "subdivide_trianglemesh_host.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
-
-static_assert(ST_SORT_BLOCK == MT_SORT_BLOCK, "the workspace is laid out for the sort's block size");
 
 constexpr unsigned long long SL_LOW = 0xffffffffull;
 
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(256) void sl_emit_kernel(const int64_t* __restrict_
   unsigned long long r[3];
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
-    const long long e = mt_rank(uniq, E, k[s]);  // in [0, E): the key is one of the sorted keys
+    const long long e = ss_rank(uniq, E, k[s]);  // in [0, E): the key is one of the sorted keys
     r[s] = V + (unsigned long long)e;
     const int slot = atomicAdd(&count[e], 1);
     if (slot < 2) opp[2 * e + slot] = (int64_t)corner[s];
@@ -104,7 +102,7 @@ __global__ __launch_bounds__(256) void sl_transposed_kernel(long long E, const u
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= E) return;
   const unsigned long long key = swapped[j];  // max << 32 | min, the j-th in ascending order
-  const long long e = mt_rank(uniq, E, (key << 32) | (key >> 32));
+  const long long e = ss_rank(uniq, E, (key << 32) | (key >> 32));
   ((ulonglong2*)tlist)[j] = make_ulonglong2(key & SL_LOW, (unsigned long long)e);
 }
 
@@ -308,27 +306,9 @@ __global__ __launch_bounds__(256) void sl_backward_opp_kernel(SlTopo tp, long lo
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-// n keys in `keys`, sorted in place through `other` (an even number of passes: low half first, then the high half)
-int sl_sort(hipStream_t st, long long n, long long V, unsigned long long* keys, unsigned long long* other, int* hist,
-            long long* hoffs, long long* sums) {
-  const long long nsb = mt_cdiv(n, MT_SORT_BLOCK);
-  const int passes = st_passes_per_half(V);
-  for (int half = 0; half < 2; ++half) {
-    for (int pass = 0; pass < passes; ++pass) {
-      const int shift = 32 * half + 8 * pass;
-      hipLaunchKernelGGL(mt_sort_hist_kernel, dim3((unsigned)nsb), dim3(256), 0, st, n, (const unsigned long long*)keys, shift, nsb,
-                         hist);
-      KAMD_CHECK(mt_scan(st, nsb * 256, hist, hoffs, sums));
-      hipLaunchKernelGGL(mt_sort_scatter_kernel, dim3((unsigned)nsb), dim3(256), 0, st, n, (const unsigned long long*)keys, shift,
-                         nsb, (const long long*)hoffs, other);
-      unsigned long long* tmp = keys;
-      keys = other;
-      other = tmp;
-    }
-  }
-  return (int)hipGetLastError();
+inline SsSortWs sl_sort_ws(char* ws, const SlLayout& l) {
+  return ss_sort_ws((int*)(ws + l.hist), (long long*)(ws + l.hoffs), (long long*)(ws + l.sums));
 }
-
 inline bool sl_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
 int sl_edges(hipStream_t st, long long F, long long V, const int64_t* faces, void* workspace, int64_t* host_num_edges) {
@@ -341,23 +321,11 @@ int sl_edges(hipStream_t st, long long F, long long V, const int64_t* faces, voi
   char* ws = (char*)workspace;
   unsigned long long* keys = (unsigned long long*)(ws + l.keys_a);
   unsigned long long* uniq = (unsigned long long*)(ws + l.keys_b);
-  int* flags = (int*)(ws + l.flags);
-  long long* pos = (long long*)(ws + l.pos);
 
-  hipLaunchKernelGGL(sl_keys_kernel, dim3(mt_grid(F, 256)), dim3(256), 0, st, faces, F, keys);
+  hipLaunchKernelGGL(sl_keys_kernel, dim3(ss_grid(F, 256)), dim3(256), 0, st, faces, F, keys);
   KAMD_CHECK(hipGetLastError());
-  KAMD_CHECK(sl_sort(st, l.n, V, keys, uniq, (int*)(ws + l.hist), (long long*)(ws + l.hoffs), (long long*)(ws + l.sums)));
-  // (the sorted keys are in keys_a again, and keys_b is free for the unique keys)
-  hipLaunchKernelGGL(mt_heads_kernel, dim3(mt_grid(l.n, 256)), dim3(256), 0, st, l.n, (const unsigned long long*)keys, flags);
-  KAMD_CHECK(mt_scan(st, l.n, flags, pos, (long long*)(ws + l.sums)));
-  hipLaunchKernelGGL(mt_unique_kernel, dim3(mt_grid(l.n, 256)), dim3(256), 0, st, l.n, (const unsigned long long*)keys,
-                     (const int*)flags, (const long long*)pos, uniq);
-  KAMD_CHECK(hipGetLastError());
-  long long h = 0;
-  KAMD_CHECK(hipMemcpyAsync(&h, pos + l.n, 8, hipMemcpyDeviceToHost, st));
-  KAMD_CHECK(hipStreamSynchronize(st));
-  *host_num_edges = h;
-  return 0;
+  KAMD_CHECK(ss_sort(st, l.n, ss_passes_halves(st_id_bits(V)), keys, uniq, keys, sl_sort_ws(ws, l)));  // in place, through keys_b
+  return ss_unique(st, l.n, keys, (int*)(ws + l.flags), (long long*)(ws + l.pos), (long long*)(ws + l.sums), uniq, host_num_edges);
 }
 
 int sl_emit(hipStream_t st, long long F, long long V, const int64_t* faces, void* workspace, long long E, int64_t* edges,
@@ -375,22 +343,22 @@ int sl_emit(hipStream_t st, long long F, long long V, const int64_t* faces, void
   unsigned long long* swapped = (unsigned long long*)(ws + l.keys_a);  // (the sorted 3 F keys are no longer needed)
   const unsigned long long* uniq = (const unsigned long long*)(ws + l.keys_b);
   KAMD_CHECK(kamd_zero_async(count, (size_t)E * 4, st));
-  hipLaunchKernelGGL(sl_edges_kernel, dim3(mt_grid(E, 256)), dim3(256), 0, st, E, uniq, edges, swapped);
-  hipLaunchKernelGGL(sl_emit_kernel, dim3(mt_grid(F, 256)), dim3(256), 0, st, faces, F, (unsigned long long)V, uniq, E, new_faces,
+  hipLaunchKernelGGL(sl_edges_kernel, dim3(ss_grid(E, 256)), dim3(256), 0, st, E, uniq, edges, swapped);
+  hipLaunchKernelGGL(sl_emit_kernel, dim3(ss_grid(F, 256)), dim3(256), 0, st, faces, F, (unsigned long long)V, uniq, E, new_faces,
                      count, opp);
   KAMD_CHECK(hipGetLastError());
-  KAMD_CHECK(sl_sort(st, E, V, swapped, (unsigned long long*)(ws + l.keys_c), (int*)(ws + l.hist), (long long*)(ws + l.hoffs),
-                     (long long*)(ws + l.sums)));
-  hipLaunchKernelGGL(sl_transposed_kernel, dim3(mt_grid(E, 256)), dim3(256), 0, st, E, uniq, (const unsigned long long*)swapped,
+  KAMD_CHECK(ss_sort(st, E, ss_passes_halves(st_id_bits(V)), swapped, (unsigned long long*)(ws + l.keys_c), swapped,
+                     sl_sort_ws(ws, l)));  // in place, through keys_c
+  hipLaunchKernelGGL(sl_transposed_kernel, dim3(ss_grid(E, 256)), dim3(256), 0, st, E, uniq, (const unsigned long long*)swapped,
                      tlist);
-  hipLaunchKernelGGL(sl_runs_kernel, dim3(mt_grid(V, 256)), dim3(256), 0, st, V, E, uniq, (const unsigned long long*)swapped, runs,
+  hipLaunchKernelGGL(sl_runs_kernel, dim3(ss_grid(V, 256)), dim3(256), 0, st, V, E, uniq, (const unsigned long long*)swapped, runs,
                      valence);
   KAMD_RETURN_LAST_ERROR();
 }
 
 // blocks of 256 over rows * 4 elements, or 0 when that many do not fit a launch
 inline long long sl_blocks(long long rows) {
-  const long long blocks = mt_cdiv(rows * 4, 256);
+  const long long blocks = ss_cdiv(rows * 4, 256);
   return blocks < (1ll << 31) ? blocks : 0;
 }
 inline bool sl_bad_value_extents(long long B, long long V, long long E) {

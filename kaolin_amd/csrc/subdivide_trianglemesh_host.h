@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "subdivide_tetmesh_host.h"  // ST_SORT_BLOCK, st_passes_per_half, st_align, st_cdiv: the same sort, the same rules
+#include "subdivide_tetmesh_host.h"  // st_id_bits, st_passes_per_half, st_align: the same keys, the same rules
 
 // V < 2^32: an id is one half of a 64-bit key.  F <= 2^35: 3 F keys in workgroups of 256 stay below 2^31 workgroups.
 inline bool sl_bad_extents(long long F, long long V) { return F < 0 || V < 0 || V >= (1ll << 32) || F > (1ll << 35); }
@@ -22,17 +22,16 @@ struct SlLayout {
 inline SlLayout sl_layout(long long F) {
   SlLayout l;
   l.n = 3 * F;
-  l.nsb = st_cdiv(l.n, ST_SORT_BLOCK);
-  const long long scan_max = l.nsb * 256 > l.n ? l.nsb * 256 : l.n;
+  l.nsb = ss_sort_blocks(l.n);
   size_t o = 0;
   l.keys_a = o, o += st_align((size_t)l.n * 8);
   l.keys_b = o, o += st_align((size_t)l.n * 8);
   l.keys_c = o, o += st_align((size_t)l.n * 8);
   l.flags = o, o += st_align((size_t)l.n * 4);
   l.pos = o, o += st_align(((size_t)l.n + 1) * 8);
-  l.hist = o, o += st_align((size_t)l.nsb * 256 * 4);
-  l.hoffs = o, o += st_align(((size_t)l.nsb * 256 + 1) * 8);
-  l.sums = o, o += st_align(((size_t)st_cdiv(scan_max, 1024) + 1) * 8);
+  l.hist = o, o += st_align(ss_sort_hist_entries(l.n) * 4);
+  l.hoffs = o, o += st_align(ss_sort_offs_entries(l.n) * 8);
+  l.sums = o, o += st_align(ss_sort_unique_sums_entries(l.n) * 8);
   l.bytes = o;
   return l;
 }

@@ -11,7 +11,7 @@ import torch
 
 import subdivide_trianglemesh_bruteforce as bf
 
-SORT_BLOCK, SCAN_BLOCK = 2048, 1024                       # csrc/tet_sort.h: MT_SORT_BLOCK, the blocks of mt_scan
+SORT_BLOCK, SCAN_BLOCK = 2048, 1024                       # csrc/sort_scan_host.h: SS_SORT_BLOCK, SS_SCAN_BLOCK
 KEY_FACES = (1, 341, 342, 682, 683, 1365, 1366, 2730, 2731)                   # 3 F next to 1024, 2048, 4096 and 8192
 KEY_COUNTS = (3, 1023, 1026, 2046, 2049, 4095, 4098, 8190, 8193)
 EDGE_COUNTS = (1, 3, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4097)

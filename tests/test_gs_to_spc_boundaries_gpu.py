@@ -1,4 +1,4 @@
-"""ops.conversions.gs_to_voxelgrid through the HIP path (csrc/gs_to_spc.hip, spc_stage.h with GsPrim) at the boundaries of its
+"""ops.conversions.gs_to_voxelgrid through the HIP path (csrc/gs_to_spc.hip, spc_stage.h with GsPrim, sort_scan.h) at the boundaries of its
 pipeline, against the numpy oracle of tests/gs_to_spc_bruteforce.py.  Integer results and cov3d_invs are compared bit for bit, the
 integral against the bound 2^-23 |w| + 2^-149 of tests/test_gs_to_spc_cpu.py.
 
@@ -27,8 +27,8 @@ pytestmark = pytest.mark.gpu
 
 GROUPS_PER_WAVE = 8        # proposals per wavefront of spc_stage_kernel (eight lanes each)
 PROPOSALS_PER_BLOCK = 32   # proposals per 256-thread block of spc_stage_kernel; pairs per block of gs_integrate_kernel
-SCAN_BLOCK = 1024          # entries per block of ms_scan
-SORT_BLOCK = 2048          # pairs per block of the radix sort (SPC_SORT_BLOCK)
+SCAN_BLOCK = 1024          # entries per block of ss_scan
+SORT_BLOCK = 2048          # pairs per block of the radix sort (SS_SORT_BLOCK)
 STAGE_LEVELS = 3
 GS_PREP = 15               # floats per Gaussian of the prepared table: AABB min, AABB max, three contact points
 

@@ -16,8 +16,8 @@ from test_gs_to_spc_cpu import (C, ISO, REF_TOL, TOL, bad_arguments, centred_gau
 pytestmark = pytest.mark.gpu
 
 PREPARE_BLOCK = 256     # Gaussians per block of gs_prepare_kernel
-SCAN_BLOCK = 1024       # entries per block of ms_scan
-SORT_BLOCK = 2048       # pairs per block of the radix sort (SPC_SORT_BLOCK)
+SCAN_BLOCK = 1024       # entries per block of ss_scan
+SORT_BLOCK = 2048       # pairs per block of the radix sort (SS_SORT_BLOCK)
 
 
 def random_cells(count, level, seed):

@@ -1,4 +1,4 @@
-"""unbatched_mesh_to_spc through the HIP path (csrc/mesh_to_spc.hip, spc_stage.h, spc_octree.h) at the block boundaries of its
+"""unbatched_mesh_to_spc through the HIP path (csrc/mesh_to_spc.hip, spc_stage.h, spc_octree.h, sort_scan.h) at the block boundaries of its
 pipeline, against the numpy references of tests/mesh_to_spc_bruteforce.py and the oracle.  Everything is compared bit for bit.
 
 (a) the whole operator: levels 10 - 15 (codes beyond 32 bits, four and five stages, five and six sort passes), triangle counts around
@@ -24,8 +24,8 @@ pytestmark = pytest.mark.gpu
 
 GROUPS_PER_WAVE = 8        # proposals per wavefront of spc_stage_kernel (eight lanes each)
 PROPOSALS_PER_BLOCK = 32   # proposals per 256-thread block of spc_stage_kernel
-SCAN_BLOCK = 1024          # entries per block of ms_scan
-SORT_BLOCK = 2048          # pairs per block of the radix sort (SPC_SORT_BLOCK): eight rounds of 256
+SCAN_BLOCK = 1024          # entries per block of ss_scan
+SORT_BLOCK = 2048          # pairs per block of the radix sort (SS_SORT_BLOCK): eight rounds of 256
 SORT_ROUND = 256
 WAVE = 64
 STAGE_LEVELS = 3

@@ -12,7 +12,7 @@ from test_pointcloud_cpu import (FLOAT_DTYPES, INT_DTYPES, VOXEL_DTYPES, check_r
 pytestmark = pytest.mark.gpu
 
 CHUNK = 128             # sorted positions per chunk of the mean (csrc/pointcloud.hip PC_CHUNK)
-SORT_BLOCK = 2048       # pairs per block of the pair sort (csrc/spc_stage.h SPC_SORT_BLOCK)
+SORT_BLOCK = 2048       # pairs per block of the pair sort (csrc/sort_scan_host.h SS_SORT_BLOCK)
 
 
 # ---- SPC -------------------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ from test_render_spc_cpu import (case, check_exponential_integration, check_pack
 
 pytestmark = pytest.mark.gpu
 
-SCAN_BLOCK = 1024       # counts per block of the scan of the hit counts (csrc/tet_sort.h)
+SCAN_BLOCK = 1024       # counts per block of the scan of the hit counts (csrc/sort_scan.h)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ tracing

@@ -15,7 +15,7 @@ from test_spc_dual_cpu import (check_backward, check_dense, check_dual, check_ex
 
 pytestmark = pytest.mark.gpu
 
-SORT_TILE = 2048        # keys per block of the radix sort (csrc/tet_sort.h MT_SORT_BLOCK): 8 keys a point -> 256 points
+SORT_TILE = 2048        # keys per block of the radix sort (csrc/sort_scan_host.h SS_SORT_BLOCK): 8 keys a point -> 256 points
 BLOCK_POINTS = 32       # points per 256-thread block of the trinket kernel: a thread per (point, corner)
 
 

@@ -13,7 +13,7 @@ from test_spc_cpu import (check_feature_grid_round_trip, check_fixture, check_pi
 pytestmark = pytest.mark.gpu
 
 SCAN_BLOCK = 1024       # bytes per block of the scan (csrc/spc.hip SP_SCAN_BLOCK)
-SORT_TILE = 2048        # keys per block of the radix sort (csrc/tet_sort.h MT_SORT_BLOCK)
+SORT_TILE = 2048        # keys per block of the radix sort (csrc/sort_scan_host.h SS_SORT_BLOCK)
 
 
 def cube_with_bytes(level, num_bytes, seed):

@@ -1,5 +1,5 @@
 """The HIP pipelines of marching_tetrahedra and subdivide_tetmesh at every stage boundary of the sort / scan / compaction they
-share (csrc/tet_sort.h), on the cases of tet_boundary_cases.py (test_tet_boundary_cases_cpu.py shows that each case sits on the
+share (csrc/sort_scan.h), on the cases of tet_boundary_cases.py (test_tet_boundary_cases_cpu.py shows that each case sits on the
 boundary it names).  The CPU side is the package's torch formulation, which the two CPU test files pin to the reference's
 records; forward results are compared bit for bit (`same`: integers are exact, floats are the same separately rounded
 operations), gradients with the project's element-wise bound against float64 CPU autograd.  No test here passes an

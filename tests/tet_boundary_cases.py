@@ -1,4 +1,4 @@
-"""Inputs that put the tetrahedral pipelines (csrc/tet_sort.h under csrc/marching_tetrahedra.hip and csrc/subdivide_tetmesh.hip)
+"""Inputs that put the tetrahedral pipelines (csrc/sort_scan.h under csrc/marching_tetrahedra.hip and csrc/subdivide_tetmesh.hip)
 on the boundaries of their sort, scans and compaction: exact numbers of crossing-edge instances and of tets around the block
 sizes 64 / 256 / 1024 / 2048, vertex counts on either side of every radix pass count, long runs of equal keys, high valence, and
 the DMTet loop.  Pure torch on the CPU, seeded by torch.Generator.  Every builder returns

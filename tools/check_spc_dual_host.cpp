@@ -26,6 +26,9 @@ int main() {
     EXPECT(8 * code <= SD_LEVEL_SHIFT && sd_code_bits(L) <= 45 && (L >> 8) == 0);
     for (int k = 0; k < all; ++k) EXPECT(sd_pass_shift(L, k) == (k < code ? 8 * k : SD_LEVEL_SHIFT));
     EXPECT(sd_level_passes(L) == (L > 0 ? 1 : 0) && sd_sorted_in_b(L) == (all % 2 == 1));
+    const SsPasses p = sd_passes(L);  // what the sort is given: the same shifts, ascending, within the key
+    EXPECT(p.count == all && p.count <= SS_MAX_PASSES);
+    for (int k = 0; k < all; ++k) EXPECT(p.shift[k] == sd_pass_shift(L, k) && p.shift[k] <= 56 && (k == 0 || p.shift[k] > p.shift[k - 1]));
     EXPECT(!sd_bad_extents(1, L));
   }
   EXPECT(sd_code_passes(0) == 1 && sd_code_passes(1) == 1 && sd_code_passes(2) == 2 && sd_code_passes(14) == 6);
@@ -54,12 +57,12 @@ int main() {
     const SdLayout l = sd_layout(n);
     const size_t bytes = sd_workspace_bytes(n, 9);
     printf("n=%lld: keys=%lld sort_blocks=%lld workspace=%zu bytes\n", n, l.keys, l.nsb, bytes);
-    EXPECT(l.keys == 8 * n && l.nsb == (l.keys + SD_SORT_BLOCK - 1) / SD_SORT_BLOCK && bytes == l.bytes);
+    EXPECT(l.keys == 8 * n && l.nsb == (l.keys + SS_SORT_BLOCK - 1) / SS_SORT_BLOCK && bytes == l.bytes);
     const long long scan_max = l.nsb * 256 > l.keys ? l.nsb * 256 : l.keys;
     const size_t off[] = {l.sizes, l.keys_a, l.keys_b, l.flags, l.pos, l.hist, l.hoffs, l.sums, l.bytes};
     const size_t need[] = {(size_t)(SD_MAX_LEVEL + 2) * 8, (size_t)l.keys * 8, (size_t)l.keys * 8, (size_t)l.keys * 4,
                            ((size_t)l.keys + 1) * 8, (size_t)l.nsb * 256 * 4, ((size_t)l.nsb * 256 + 1) * 8,
-                           ((size_t)sd_cdiv(scan_max, 1024) + 1) * 8};
+                           ((size_t)ss_cdiv(scan_max, 1024) + 1) * 8};
     for (int k = 0; k < 8; ++k) EXPECT(off[k] % 256 == 0 && off[k + 1] >= off[k] + need[k]);
     EXPECT(bytes >= (size_t)l.keys * 28);  // 8 + 8 + 4 + 8 bytes a key: more than 2^32 for the large n, no 32-bit wrap
     if (n <= 257) {                        // the layout used as offsets into a real buffer

@@ -36,7 +36,7 @@ int main() {
         EXPECT(bytes == 0);
         continue;
       }
-      EXPECT(l.n == 6 * T && l.nsb == (l.n + ST_SORT_BLOCK - 1) / ST_SORT_BLOCK && bytes == l.bytes);
+      EXPECT(l.n == 6 * T && l.nsb == (l.n + SS_SORT_BLOCK - 1) / SS_SORT_BLOCK && bytes == l.bytes);
       // the buffers, in order, each 16-byte aligned and large enough, none overlapping the next
       const size_t off[] = {l.keys_a, l.keys_b, l.flags, l.pos, l.hist, l.hoffs, l.sums, l.bytes};
       const size_t need[] = {(size_t)l.n * 8, (size_t)l.n * 8, (size_t)l.n * 4, ((size_t)l.n + 1) * 8, (size_t)l.nsb * 256 * 4,

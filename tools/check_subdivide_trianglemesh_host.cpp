@@ -37,13 +37,13 @@ int main() {
         EXPECT(bytes == 0);
         continue;
       }
-      EXPECT(l.n == 3 * F && l.nsb == (l.n + ST_SORT_BLOCK - 1) / ST_SORT_BLOCK && bytes == l.bytes);
+      EXPECT(l.n == 3 * F && l.nsb == (l.n + SS_SORT_BLOCK - 1) / SS_SORT_BLOCK && bytes == l.bytes);
       // the buffers, in order, each 16-byte aligned and large enough, none overlapping the next; the second sort (E <= 3 F
       // keys) fits the buffers sized for the first
       const size_t off[] = {l.keys_a, l.keys_b, l.keys_c, l.flags, l.pos, l.hist, l.hoffs, l.sums, l.bytes};
       const size_t need[] = {(size_t)l.n * 8, (size_t)l.n * 8, (size_t)l.n * 8, (size_t)l.n * 4, ((size_t)l.n + 1) * 8,
                              (size_t)l.nsb * 256 * 4, ((size_t)l.nsb * 256 + 1) * 8,
-                             ((size_t)st_cdiv(l.nsb * 256 > l.n ? l.nsb * 256 : l.n, 1024) + 1) * 8};
+                             ((size_t)ss_cdiv(l.nsb * 256 > l.n ? l.nsb * 256 : l.n, 1024) + 1) * 8};
       for (int k = 0; k < 8; ++k) EXPECT(off[k] % 16 == 0 && off[k + 1] >= off[k] + need[k]);
       EXPECT(bytes >= (size_t)l.n * 36);  // 8 + 8 + 8 + 4 + 8 bytes a key: more than 2^32 for the large F, no 32-bit wrap
       if (F <= 720) {                     // the layout used as offsets into a real buffer
