@@ -1355,6 +1355,46 @@ int kamd_pointcloud_voxelgrids_f64(void* stream, int64_t B, int64_t P, int R, do
                                    const double* origin, const double* scale, int sparse, void* out);
 
 /* ------------------------------------------------------------------------- */
+/* ops.mesh per-vertex sums / means of per-face-corner features               */
+/* (csrc/vertex_features.hip: average_face_vertex_features,                    */
+/* compute_vertex_normals, the sum of vertex_tangents; the reference uses      */
+/* scatter_add_, these entry points exist only on our side).                   */
+/* faces: (F, K) int32 (faces_bytes 4) or int64 (8) with element strides; V    */
+/* vertices; F, K, V >= 1, F K < 2^31 - 1, V < 2^31 - 1.                       */
+/* corners_build: offsets (V + 1) and corners (K F) int32: corners[offsets[v]  */
+/*   .. offsets[v + 1]) = the corners i = k F + f with faces[f, k] == v in     */
+/*   ascending i (the stable keys-only sort over the low ceil(log2 V) bits of  */
+/*   (i << 32) | v, a binary search per offset).  *host_bad = the number of    */
+/*   ids outside [0, V) (they are filed under vertex 0: the caller raises) --  */
+/*   the ONE host read; the call synchronises the stream.  workspace:          */
+/*   kamd_vertex_corners_workspace(F, K, V) bytes (0: extents out of range).   */
+/* gather_*: face_features (B, F, K, N) with element strides (0 allowed) ->    */
+/*   out (B, V, N) contiguous: per (b, v, n) the sum over the vertex's corners */
+/*   in list order, one rounded addition per corner from +0; mean != 0: one    */
+/*   division by max(count, 1).  One launch, no atomics, no host read.         */
+/* gather_backward_*: grad_out (B, V, N) with element strides -> grad          */
+/*   (B, F, K, N) contiguous, grad[b, f, k, :] = grad_out[b, faces[f, k], :]   */
+/*   (mean != 0: / max(count, 1), count = offsets[v + 1] - offsets[v]); an id  */
+/*   outside [0, V) takes 0.  One launch.                                      */
+/* ------------------------------------------------------------------------- */
+size_t kamd_vertex_corners_workspace(int64_t F, int64_t K, int64_t V);
+int kamd_vertex_corners_build(void* stream, int64_t F, int64_t K, int64_t V, const void* faces, int faces_bytes, int64_t stride_f,
+                              int64_t stride_k, void* workspace, size_t workspace_bytes, int32_t* offsets, int32_t* corners,
+                              int32_t* host_bad);
+int kamd_vertex_gather_f32(void* stream, int64_t B, int64_t F, int64_t K, int64_t V, int64_t N, const float* face_features,
+                           int64_t stride_b, int64_t stride_f, int64_t stride_k, int64_t stride_n, const int32_t* offsets,
+                           const int32_t* corners, int mean, float* out);
+int kamd_vertex_gather_f64(void* stream, int64_t B, int64_t F, int64_t K, int64_t V, int64_t N, const double* face_features,
+                           int64_t stride_b, int64_t stride_f, int64_t stride_k, int64_t stride_n, const int32_t* offsets,
+                           const int32_t* corners, int mean, double* out);
+int kamd_vertex_gather_backward_f32(void* stream, int64_t B, int64_t F, int64_t K, int64_t V, int64_t N, const float* grad_out,
+                                    int64_t stride_b, int64_t stride_v, int64_t stride_n, const void* faces, int faces_bytes,
+                                    int64_t faces_stride_f, int64_t faces_stride_k, const int32_t* offsets, int mean, float* grad);
+int kamd_vertex_gather_backward_f64(void* stream, int64_t B, int64_t F, int64_t K, int64_t V, int64_t N, const double* grad_out,
+                                    int64_t stride_b, int64_t stride_v, int64_t stride_n, const void* faces, int faces_bytes,
+                                    int64_t faces_stride_f, int64_t faces_stride_k, const int32_t* offsets, int mean, double* grad);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -1708,9 +1708,109 @@ def pointclouds_to_voxelgrids_cuda(pointclouds, resolution, origin, scale, retur
         return torch.sparse_coo_tensor(idx, torch.ones(idx.shape[1], dtype=dtype, device=dev), (B, R, R, R), is_coalesced=True)
 
 
+# ---- kaolin._C.ops.mesh: per-vertex sums / means on csrc/vertex_features.hip (no reference counterpart: scatter_add_ there) ---------
+def _vf_extents(fn, F, K, V):
+    if not (F >= 1 and K >= 1 and V >= 1):
+        raise ValueError(f'{fn}: faces of shape ({F}, {K}) and {V} vertices: every extent must be at least 1')
+    if F * K >= 2 ** 31 - 1:
+        raise ValueError(f'{fn}: {F} x {K} face corners: the corner lists hold int32, K F must stay below 2^31 - 1')
+    if V >= 2 ** 31 - 1:
+        raise ValueError(f'{fn}: {V} vertices: the corner lists hold int32, V must stay below 2^31 - 1')
+
+
+def _vf_faces(fn, faces):
+    torch_check(isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dim() == 2, f'{fn}: faces must be a CUDA tensor of size (F, K)')
+    torch_check(faces.dtype in (torch.int32, torch.int64), f'{fn}: faces must be int or long')
+    return faces.detach()
+
+
+def vertex_corners_cuda(faces, num_vertices):
+    """faces (F, K) int / long of any strides -> (offsets (V + 1) int32, corners (K F) int32): ``corners[offsets[v]:offsets[v + 1]]``
+    are the corners ``i = k F + f`` with ``faces[f, k] == v`` in ascending ``i``, i.e. (corner slot, then face) order.
+
+    Launches: 2 (clear, keys) + 4 per 8 bits of ceil(log2 V) (the keys-only sort; V = 1: one copy) + 1 (lists).  ONE host read (the
+    count of ids outside [0, V): ``IndexError``); the call synchronises the current stream and cannot be captured in a graph.
+    ``ValueError`` before any launch when K F or V reaches 2^31 - 1."""
+    fn = 'vertex_corners_cuda'
+    faces = _vf_faces(fn, faces)
+    F, K, V, dev = faces.size(0), faces.size(1), int(num_vertices), faces.device
+    _vf_extents(fn, F, K, V)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_vertex_corners_workspace(F, K, V)
+        ws = _lib.workspace(nbytes, dev)
+        offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
+        corners = torch.empty(F * K, dtype=torch.int32, device=dev)
+        bad = ctypes.c_int32(0)
+        _lib.check(lib.kamd_vertex_corners_build(_lib.stream_ptr(dev), F, K, V, _lib.ptr(faces), faces.element_size(), faces.stride(0),
+                                                 faces.stride(1), _lib.ptr(ws), nbytes, _lib.ptr(offsets), _lib.ptr(corners),
+                                                 ctypes.cast(ctypes.pointer(bad), ctypes.c_void_p)), fn)
+    if bad.value != 0:                                                       # the one host read
+        raise IndexError(f'{fn}: {bad.value} of the {F * K} face corners hold a vertex id outside [0, {V})')
+    return offsets, corners
+
+
+def _vf_lists(fn, offsets, corners, V, n, dev):
+    torch_check(isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int32 and offsets.device == dev and
+                offsets.is_contiguous() and tuple(offsets.shape) == (V + 1,), f'{fn}: offsets must be a contiguous int tensor of size ({V + 1},)')
+    if corners is not None:
+        torch_check(isinstance(corners, torch.Tensor) and corners.dtype == torch.int32 and corners.device == dev and
+                    corners.is_contiguous() and tuple(corners.shape) == (n,), f'{fn}: corners must be a contiguous int tensor of size ({n},)')
+
+
+def vertex_gather_forward_cuda(face_features, offsets, corners, num_vertices, mean):
+    """face_features (B, F, K, N) float / double of any strides (0 included) + the lists of vertex_corners_cuda -> (B, V, N): per
+    vertex the sum of its corners' features in list order, one rounded addition per corner; ``mean``: divided once by
+    max(count, 1).  One launch, no atomics, no host read: capturable, and two calls give the same bits."""
+    fn = 'vertex_gather_forward_cuda'
+    torch_check(isinstance(face_features, torch.Tensor) and face_features.is_cuda and face_features.dim() == 4,
+                f'{fn}: face_features must be a CUDA tensor of size (B, F, K, N)')
+    sfx = _lib.dtype_suffix(face_features.dtype, fn)
+    x = face_features.detach()
+    (B, F, K, N), V, dev = x.shape, int(num_vertices), x.device
+    _vf_extents(fn, F, K, V)
+    torch_check(B >= 1 and N >= 1, f'{fn}: face_features of size {tuple(x.shape)}: every extent must be at least 1')
+    _vf_lists(fn, offsets, corners, V, F * K, dev)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.empty((B, V, N), dtype=x.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_vertex_gather_{sfx}')(_lib.stream_ptr(dev), B, F, K, V, N, _lib.ptr(x), x.stride(0), x.stride(1),
+                                                            x.stride(2), x.stride(3), _lib.ptr(offsets), _lib.ptr(corners),
+                                                            1 if mean else 0, _lib.ptr(out)), fn)
+    return out
+
+
+def vertex_gather_backward_cuda(grad_out, faces, offsets, mean):
+    """grad_out (B, V, N) float / double of any strides, faces (F, K) int / long, offsets (V + 1) -> contiguous (B, F, K, N):
+    ``grad[b, f, k, :] = grad_out[b, faces[f, k], :]``, divided by max(count, 1) with ``mean`` (the reference's autograd expression:
+    one division).  One launch, no host read."""
+    fn = 'vertex_gather_backward_cuda'
+    torch_check(isinstance(grad_out, torch.Tensor) and grad_out.is_cuda and grad_out.dim() == 3,
+                f'{fn}: grad_out must be a CUDA tensor of size (B, V, N)')
+    sfx = _lib.dtype_suffix(grad_out.dtype, fn)
+    faces = _vf_faces(fn, faces)
+    g = grad_out.detach()
+    (B, V, N), (F, K), dev = g.shape, faces.shape, g.device
+    torch_check(faces.device == dev, f'{fn}: faces must be on the device of grad_out')
+    _vf_extents(fn, F, K, V)
+    torch_check(B >= 1 and N >= 1, f'{fn}: grad_out of size {tuple(g.shape)}: every extent must be at least 1')
+    _vf_lists(fn, offsets, None, V, F * K, dev)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad = torch.empty((B, F, K, N), dtype=g.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_vertex_gather_backward_{sfx}')(_lib.stream_ptr(dev), B, F, K, V, N, _lib.ptr(g), g.stride(0),
+                                                                     g.stride(1), g.stride(2), _lib.ptr(faces), faces.element_size(),
+                                                                     faces.stride(0), faces.stride(1), _lib.ptr(offsets),
+                                                                     1 if mean else 0, _lib.ptr(grad)), fn)
+    return grad
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
+                              vertex_corners_cuda=vertex_corners_cuda,
+                              vertex_gather_forward_cuda=vertex_gather_forward_cuda,
+                              vertex_gather_backward_cuda=vertex_gather_backward_cuda,
                               subdivide_trianglemesh_cuda=subdivide_trianglemesh_cuda,
                               trianglemesh_loop_forward_cuda=trianglemesh_loop_forward_cuda,
                               trianglemesh_loop_backward_cuda=trianglemesh_loop_backward_cuda,

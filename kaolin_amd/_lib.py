@@ -148,6 +148,13 @@ SIGNATURES.update({
 })
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_pointcloud_voxelgrids_{_t}'] = (_i, [_vp, _i64, _i64, _i, _dbl, _vp, _vp, _vp, _i, _vp])
+SIGNATURES.update({
+    'kamd_vertex_corners_workspace': (_sz, [_i64, _i64, _i64]),
+    'kamd_vertex_corners_build': (_i, [_vp, _i64, _i64, _i64, _vp, _i, _i64, _i64, _vp, _sz, _vp, _vp, _vp]),
+})
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_vertex_gather_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] + [_i64] * 4 + [_vp, _vp, _i, _vp])
+    SIGNATURES[f'kamd_vertex_gather_backward_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] + [_i64] * 3 + [_vp, _i, _i64, _i64, _vp, _i, _vp])
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):

@@ -1,10 +1,13 @@
 """Mesh helpers on the DIB-R path (pure torch): per-face gathers and normals, plus the vertex-set
 subdivision the voxelizer's definition rests on; the tetrahedral-mesh operators of tetmesh.py (subdivide_tetmesh on a HIP
-edge-midpoint pipeline); and subdivide_trianglemesh of trianglemesh.py (Loop subdivision with a per-vertex alpha, on HIP)."""
+edge-midpoint pipeline); subdivide_trianglemesh of trianglemesh.py (Loop subdivision with a per-vertex alpha, on HIP); and the
+per-vertex averages of vertex_features.py (average_face_vertex_features, compute_vertex_normals, vertex_tangents on a deterministic
+HIP gather, unindex_vertices_by_faces)."""
 import torch
 
 __all__ = ['index_vertices_by_faces', 'face_normals', 'check_sign', 'adjacency_matrix', 'uniform_laplacian',
-           'subdivide_tetmesh', 'inverse_vertices_offset', 'subdivide_trianglemesh']
+           'subdivide_tetmesh', 'inverse_vertices_offset', 'subdivide_trianglemesh', 'average_face_vertex_features',
+           'compute_vertex_normals', 'unindex_vertices_by_faces', 'vertex_tangents']
 
 
 def index_vertices_by_faces(vertices_features, faces):
@@ -175,3 +178,6 @@ from . import tetmesh  # noqa: E402
 from .tetmesh import subdivide_tetmesh, inverse_vertices_offset  # noqa: E402
 from . import trianglemesh  # noqa: E402
 from .trianglemesh import subdivide_trianglemesh  # noqa: E402
+from . import vertex_features  # noqa: E402
+from .vertex_features import (average_face_vertex_features, compute_vertex_normals, unindex_vertices_by_faces,  # noqa: E402
+                              vertex_tangents)

@@ -27,8 +27,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ... import _C
+from .vertex_features import vertex_tangents  # noqa: F401  (the reference keeps it in trianglemesh.py)
 
-__all__ = ['subdivide_trianglemesh']
+__all__ = ['subdivide_trianglemesh', 'vertex_tangents']
 
 # The four children of a face, in order; `xy` is the new vertex of the edge slot xy.  csrc/subdivide_trianglemesh.hip spells out
 # the same rows.  CHILD_FACES holds them as columns of (a, b, c, ab, bc, ca).
