@@ -964,6 +964,60 @@ int kamd_cubic_meshes_emit_faces(void* stream, int64_t B, int X, int Y, int Z, c
                                  int64_t* faces);
 
 /* ------------------------------------------------------------------------- */
+/* ops.conversions.voxelgrids_to_trianglemeshes: marching cubes (reference:    */
+/* kaolin/csrc/ops/conversions/unbatched_mcube; csrc/mcube.hip has the         */
+/* pipeline, csrc/mcube_table.h the generated case table).  voxelgrids:        */
+/* (B,X,Y,Z), X,Y,Z >= 1, with ELEMENT strides (any layout, read in place); u8 */
+/* also serves bool, f16 is the raw half.  border != 0: the field is the grid  */
+/* inside a border of zeros, voxel n at coordinate n + 1, a lattice of         */
+/* (X+1)(Y+1)(Z+1) cells; border == 0: the grid as given, the cells between    */
+/* its points, a lattice of X Y Z points.  3 x lattice < 2^31 per item.        */
+/* iso_value must not be NaN.  One `workspace` of kamd_mcube_workspace(...)    */
+/* bytes (host arithmetic; 0 = nothing to do or beyond the 32-bit range),      */
+/* 16-byte aligned, carries the state from step to step:                       */
+/*   1. classify_*: the case byte per cell and two counts per workgroup        */
+/*      (own vertices, triangles).                                             */
+/*   2. scan: exclusive scans of the counts; host_totals (B,2) uint32 <- per   */
+/*      item the vertices and the triangles.  Reads them back: SYNCHRONISES    */
+/*      the stream (not capturable in a graph).                                */
+/*   3. emit_vertices_*: verts (verts_rows = sum V_b, 3) float32, the items    */
+/*      one after the other, ordered by the lower end of the vertex' lattice   */
+/*      edge in raster order, then by axis; and every cell's first vertex id.  */
+/*   4. emit_faces: faces (faces_rows = sum F_b, 3) int64, ids local to the    */
+/*      item, cells in raster order.  Needs step 3.                            */
+/* Steps 3 and 4 are skipped by the caller when nothing is to be written.      */
+/*   backward_*: after steps 1-3 with border != 0, on the same grid and        */
+/*      workspace: grad_voxelgrids (B,X,Y,Z) contiguous, of the grid's type,   */
+/*      <- the gradient of the vertex positions, float32 accumulation in a     */
+/*      fixed order; fully written, one launch, no atomics.                    */
+/* ------------------------------------------------------------------------- */
+size_t kamd_mcube_workspace(int64_t B, int X, int Y, int Z, int border);
+int kamd_mcube_classify_u8(void* stream, int64_t B, int X, int Y, int Z, int border, const uint8_t* voxelgrids, int64_t stride_n,
+                           int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace);
+int kamd_mcube_classify_f16(void* stream, int64_t B, int X, int Y, int Z, int border, const void* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace);
+int kamd_mcube_classify_f32(void* stream, int64_t B, int X, int Y, int Z, int border, const float* voxelgrids, int64_t stride_n,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace);
+int kamd_mcube_scan(void* stream, int64_t B, int X, int Y, int Z, int border, void* workspace, uint32_t* host_totals);
+int kamd_mcube_emit_vertices_u8(void* stream, int64_t B, int X, int Y, int Z, int border, const uint8_t* voxelgrids, int64_t stride_n,
+                                int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace, float* verts,
+                                int64_t verts_rows);
+int kamd_mcube_emit_vertices_f16(void* stream, int64_t B, int X, int Y, int Z, int border, const void* voxelgrids, int64_t stride_n,
+                                 int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace, float* verts,
+                                 int64_t verts_rows);
+int kamd_mcube_emit_vertices_f32(void* stream, int64_t B, int X, int Y, int Z, int border, const float* voxelgrids, int64_t stride_n,
+                                 int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace, float* verts,
+                                 int64_t verts_rows);
+int kamd_mcube_emit_faces(void* stream, int64_t B, int X, int Y, int Z, int border, const void* workspace, int64_t* faces,
+                          int64_t faces_rows);
+int kamd_mcube_backward_f16(void* stream, int64_t B, int X, int Y, int Z, const void* voxelgrids, int64_t stride_n, int64_t stride_x,
+                            int64_t stride_y, int64_t stride_z, float iso_value, const void* workspace, const float* grad_verts,
+                            int64_t verts_rows, void* grad_voxelgrids);
+int kamd_mcube_backward_f32(void* stream, int64_t B, int X, int Y, int Z, const float* voxelgrids, int64_t stride_n, int64_t stride_x,
+                            int64_t stride_y, int64_t stride_z, float iso_value, const void* workspace, const float* grad_verts,
+                            int64_t verts_rows, float* grad_voxelgrids);
+
+/* ------------------------------------------------------------------------- */
 /* metrics.tetmesh: tetrahedron_volume, equivolume, amips (reference: chains   */
 /* of 10-20 torch kernels, kaolin/metrics/tetmesh.py; csrc/tetmesh_metrics.hip */
 /* has the kernels).  tet_vertices (B,T,4,3): every item's (T,4,3) block is    */

@@ -355,6 +355,118 @@ def voxelgrids_to_cubic_meshes_cuda(voxelgrids, is_trimesh=True):
     return (list(torch.split(verts, nv)), list(torch.split(faces, [(2 if is_trimesh else 1) * n for n in nq])))
 
 
+def _mcube_forward(fn, voxelgrids, iso_value, border):
+    """The four steps of csrc/mcube.hip on voxelgrids (B, X, Y, Z), B >= 1 and X, Y, Z >= 1 -> (verts (sum V_b, 3) float32,
+    faces (sum F_b, 3) int64, [V_b], [F_b], the grid as the kernels read it, the workspace).  The last two are what the backward
+    needs: the case bytes and every cell's first vertex id live in the workspace."""
+    v = voxelgrids.detach()
+    sfx = _CUBIC_SUFFIX.get(v.dtype)
+    if sfx is None:
+        v = v.float()
+        sfx = 'f32'
+    B, X, Y, Z = v.shape
+    dev = v.device
+    lattice = (X + 1) * (Y + 1) * (Z + 1) if border else X * Y * Z
+    torch_check(3 * lattice < 2 ** 31, f'{fn}: a lattice of {lattice} points holds up to {3 * lattice} vertices: '
+                                       f'more than 32-bit indices cover')
+    iso_value = float(iso_value)
+    torch_check(iso_value == iso_value, f'{fn}: iso_value must not be NaN')
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    border = 1 if border else 0
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_mcube_workspace(B, X, Y, Z, border)
+        torch_check(nbytes > 0, f'{fn}: a batch of {B} grids of {X} x {Y} x {Z} is beyond the launch range')
+        ws = _lib.workspace(nbytes, dev)
+        grid = (sp, B, X, Y, Z, border, _lib.ptr(v), *v.stride(), iso_value, _lib.ptr(ws))
+        _lib.check(getattr(lib, f'kamd_mcube_classify_{sfx}')(*grid), fn)
+        host = (ctypes.c_uint32 * (2 * B))()
+        _lib.check(lib.kamd_mcube_scan(sp, B, X, Y, Z, border, _lib.ptr(ws), ctypes.cast(host, ctypes.c_void_p)), fn)
+        totals = list(host)                                    # data-dependent sizes: the one host read
+        nv, nf = totals[0::2], totals[1::2]
+        verts = torch.empty((sum(nv), 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((sum(nf), 3), dtype=torch.long, device=dev)
+        if verts.numel() > 0:
+            _lib.check(getattr(lib, f'kamd_mcube_emit_vertices_{sfx}')(*grid, _lib.ptr(verts), verts.shape[0]), fn)
+        if faces.numel() > 0:
+            _lib.check(lib.kamd_mcube_emit_faces(sp, B, X, Y, Z, border, _lib.ptr(ws), _lib.ptr(faces), faces.shape[0]), fn)
+    return verts, faces, nv, nf, v, ws
+
+
+def _mcube_check(fn, voxelgrids):
+    torch_check(isinstance(voxelgrids, torch.Tensor) and voxelgrids.is_cuda, f'{fn}: voxelgrids must be a CUDA tensor')
+    torch_check(voxelgrids.dim() == 4, f'{fn}: voxelgrids must of size {{batch_size, X, Y, Z}}')
+    torch_check(voxelgrids.shape[0] == 0 or min(voxelgrids.shape[1:]) >= 1, f'{fn}: X, Y and Z must be at least 1')
+
+
+def voxelgrids_to_trianglemeshes_cuda(voxelgrids, iso_value=0.5):
+    """kaolin.ops.conversions.voxelgrids_to_trianglemeshes on the HIP pipeline of csrc/mcube.hip, batched (the reference's
+    operator is ``unbatched_mcube_forward_cuda`` below, once per item, on a padded float copy).  voxelgrids (B, X, Y, Z), any
+    strides; bool / uint8 / half / float are read in place, any other dtype is cast once with ``.float()``; the border of zeros
+    is implicit -> (verts, faces): two lists of B tensors, verts[b] (V_b, 3) float32 and faces[b] (F_b, 3) int64, views of one
+    vertex buffer and one face buffer for the batch.  Result sizes depend on the data: the host reads the B x 2 totals once, so
+    the call synchronises the current stream and cannot be captured in a graph."""
+    fn = 'voxelgrids_to_trianglemeshes_cuda'
+    _mcube_check(fn, voxelgrids)
+    if voxelgrids.shape[0] == 0:
+        return [], []
+    verts, faces, nv, nf = _mcube_forward(fn, voxelgrids, iso_value, True)[:4]
+    return list(torch.split(verts, nv)), list(torch.split(faces, nf))
+
+
+def mcube_forward_cuda(voxelgrids, iso_value):
+    """The forward of the differentiable operator: voxelgrids (B, X, Y, Z) half or float, B >= 1 -> (the vertex buffer, the
+    face buffer, [V_b], [F_b], state); ``state`` is the pipeline's workspace, for ``mcube_backward_cuda`` with the same grid."""
+    fn = 'mcube_forward_cuda'
+    _mcube_check(fn, voxelgrids)
+    torch_check(voxelgrids.dtype in (torch.float16, torch.float32) and voxelgrids.shape[0] > 0,
+                f'{fn}: voxelgrids must be a non-empty batch of half or float')
+    verts, faces, nv, nf, _, ws = _mcube_forward(fn, voxelgrids, iso_value, True)
+    return verts, faces, nv, nf, ws
+
+
+def mcube_backward_cuda(grad_verts, voxelgrids, iso_value, state):
+    """grad_verts (sum V_b, 3), the grid and the state of ``mcube_forward_cuda`` -> the gradient of the grid, contiguous, in its
+    dtype: one launch, one thread per grid value gathering over its six lattice edges in a fixed order (float32), no atomics."""
+    fn = 'mcube_backward_cuda'
+    _mcube_check(fn, voxelgrids)
+    sfx = {torch.float16: 'f16', torch.float32: 'f32'}.get(voxelgrids.dtype)
+    torch_check(sfx is not None and voxelgrids.shape[0] > 0, f'{fn}: voxelgrids must be a non-empty batch of half or float')
+    v = voxelgrids.detach()
+    B, X, Y, Z = v.shape
+    dev = v.device
+    lib = _lib.load()
+    torch_check(isinstance(state, torch.Tensor) and state.device == dev and state.dtype == torch.int64 and state.is_contiguous()
+                and state.numel() * 8 >= lib.kamd_mcube_workspace(B, X, Y, Z, 1) > 0,
+                f'{fn}: state is not the workspace of this grid')
+    torch_check(grad_verts.device == dev and grad_verts.dim() == 2 and grad_verts.shape[1] == 3,
+                f'{fn}: grad_verts must be of size {{num_vertices, 3}} on the device of voxelgrids')
+    g = grad_verts.detach().float().contiguous()
+    with _lib.on_device(dev):
+        grad = torch.empty((B, X, Y, Z), dtype=v.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_mcube_backward_{sfx}')(_lib.stream_ptr(dev), B, X, Y, Z, _lib.ptr(v), *v.stride(),
+                                                              float(iso_value), _lib.ptr(state), _lib.ptr(g), g.shape[0],
+                                                              _lib.ptr(grad)), fn)
+    return grad
+
+
+def unbatched_mcube_forward_cuda(voxelgrid, iso_value):
+    """The reference's operator, by its name: one (X, Y, Z) float grid AS GIVEN -- no implicit border: the cells between the given
+    points, coordinates equal to the index -> (vertices (V, 3) float32, faces (F, 3) int64), in this package's vertex and
+    triangle order (see ops.conversions.voxelgrids_to_trianglemeshes).  The reference's Python layer pads the grid and calls this
+    per item; bound to this ``_C`` it gives the meshes of our public function.  Unlike the reference's kernel there is no cap on
+    the vertices, a grid that is not a cube is indexed correctly, and the last layer of points starts no cells."""
+    fn = 'unbatched_mcube_forward_cuda'
+    torch_check(isinstance(voxelgrid, torch.Tensor) and voxelgrid.is_cuda, f'{fn}: voxelgrid must be a CUDA tensor')
+    torch_check(voxelgrid.dim() == 3, f'{fn}: voxelgrid must of size {{X, Y, Z}}')
+    torch_check(voxelgrid.dtype == torch.float32, f'{fn}: voxelgrid must be a float tensor')
+    if min(voxelgrid.shape) < 2:                               # no cell between the points
+        return (torch.zeros((0, 3), dtype=torch.float32, device=voxelgrid.device),
+                torch.zeros((0, 3), dtype=torch.long, device=voxelgrid.device))
+    verts, faces = _mcube_forward(fn, voxelgrid.unsqueeze(0), iso_value, False)[:2]
+    return verts, faces
+
+
 def check_tets_in_range(tets, num_vertices, fn='marching_tetrahedra'):
     """tets (T, 4) of an integer dtype on any device: raises IndexError when an entry lies outside [0, num_vertices).  Pure
     torch (one min / max pass and one host read); called before any kernel sees the ids -- an id out of range would make the
@@ -1820,6 +1932,9 @@ mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_in
 conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching_tetrahedra_cuda=marching_tetrahedra_cuda,
                                      marching_tetrahedra_backward_cuda=marching_tetrahedra_backward_cuda,
                                      voxelgrids_to_cubic_meshes_cuda=voxelgrids_to_cubic_meshes_cuda,
+                                     voxelgrids_to_trianglemeshes_cuda=voxelgrids_to_trianglemeshes_cuda,
+                                     unbatched_mcube_forward_cuda=unbatched_mcube_forward_cuda,
+                                     mcube_forward_cuda=mcube_forward_cuda, mcube_backward_cuda=mcube_backward_cuda,
                                      gs_to_spc_cuda=gs_to_spc_cuda, integrate_gs_cuda=integrate_gs_cuda,
                                      pointcloud_to_spc_cuda=pointcloud_to_spc_cuda,
                                      pointclouds_to_voxelgrids_cuda=pointclouds_to_voxelgrids_cuda)

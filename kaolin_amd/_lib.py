@@ -173,6 +173,16 @@ for _t in ('u8', 'i32', 'i64', 'f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_voxelgrid_fill_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp])
 for _t in ('u8', 'f16', 'f32'):
     SIGNATURES[f'kamd_cubic_meshes_classify_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _vp])
+SIGNATURES.update({
+    'kamd_mcube_workspace': (_sz, [_i64, _i, _i, _i, _i]),
+    'kamd_mcube_scan': (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    'kamd_mcube_emit_faces': (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp, _i64]),
+})
+for _t in ('u8', 'f16', 'f32'):
+    SIGNATURES[f'kamd_mcube_classify_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _f, _vp])
+    SIGNATURES[f'kamd_mcube_emit_vertices_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _f, _vp, _vp, _i64])
+for _t in ('f16', 'f32'):
+    SIGNATURES[f'kamd_mcube_backward_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _f, _vp, _vp, _i64, _vp])
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_marching_tetrahedra_classify_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_marching_tetrahedra_emit_{_t}'] = (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp])
