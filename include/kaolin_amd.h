@@ -1018,6 +1018,59 @@ int kamd_mcube_backward_f32(void* stream, int64_t B, int X, int Y, int Z, const 
                             int64_t verts_rows, float* grad_voxelgrids);
 
 /* ------------------------------------------------------------------------- */
+/* ops.conversions.FlexiCubes: differentiable dual marching cubes, float32     */
+/* (the reference is pure PyTorch, kaolin/ops/conversions/flexicubes; no _C    */
+/* operator).  csrc/flexicubes.hip has the pipeline, csrc/flexicubes_table.h   */
+/* the generated case tables.  vertices (V,3) and sdf (V,) contiguous float32, */
+/* V < 2^31; cube_idx (C,8) int64 with ELEMENT strides, C = rx ry rz cubes laid */
+/* out x ry rz + y rz + z, 12 C < 2^31; beta (C,12), alpha (C,8), gamma (C,)   */
+/* raw weights, contiguous, NULL = ones.  Steps, in this order:                */
+/*   1. classify: the case byte per cube (ambiguity rule applied) into         */
+/*      `workspace` (kamd_flexicubes_workspace(C) bytes, 16-byte aligned), and */
+/*      host_totals[9] <- per count class k = 1..4 the cubes [k-1] and the      */
+/*      (dual vertex, edge) incidences [4+k-1]; [8] != 0: an id of cube_idx     */
+/*      lies outside [0, V) (nothing was read through it; stop here).          */
+/*      S = sum cubes, num_vd = sum k cubes_k.  HOST READ: synchronises.       */
+/*   2. edges (S > 0): surf (S,4) int32 <- per surface cube (cube, case, first */
+/*      dual vertex, first incidence); the pairs of its 12 edges sorted into   */
+/*      `edges_workspace` (kamd_flexicubes_edges_workspace(S) bytes);          */
+/*      *host_num_quads <- crossed edges shared by four cubes.  HOST READ.     */
+/*   3. faces (num_quads > 0): quads (Q,4) int32 dual-vertex ids, quad_of      */
+/*      (12 S) int32 <- 4 quad + corner of (surface cube, edge) or -1, faces   */
+/*      (faces_rows,3) int64, faces_rows = 2 Q, or 4 Q with training (centre   */
+/*      vertex num_vd + quad).                                                 */
+/*   4. forward: out_vertices rows [0, num_vd), vd_gamma (num_vd), l_dev       */
+/*      (num_incidences).  No atomics.  centers (training, Q > 0):             */
+/*      out_vertices rows [num_vd, num_vd + Q).                                */
+/*   backward: grad_x (V,3), grad_sdf (V,), grad_beta, grad_alpha, grad_gamma  */
+/*      (shapes of the weights; NULL with its weight) must arrive ZEROED.      */
+/*      grad_x / grad_sdf are accumulated with float atomics; the weights'     */
+/*      rows are written by their owner.  grad_gamma only with training.       */
+/* Not capturable in a graph (two host reads).                                 */
+/* ------------------------------------------------------------------------- */
+size_t kamd_flexicubes_workspace(int64_t C);
+int kamd_flexicubes_classify(void* stream, int64_t V, int64_t C, int rx, int ry, int rz, const float* sdf, const int64_t* cube_idx,
+                             int64_t stride_cube, int64_t stride_corner, void* workspace, uint32_t* host_totals);
+size_t kamd_flexicubes_edges_workspace(int64_t S);
+int kamd_flexicubes_edges(void* stream, int64_t V, int64_t C, int64_t S, const float* sdf, const int64_t* cube_idx, int64_t stride_cube,
+                          int64_t stride_corner, const void* workspace, int32_t* surf, void* edges_workspace, int64_t* host_num_quads);
+int kamd_flexicubes_faces(void* stream, int64_t C, int64_t S, int64_t num_vd, int64_t num_quads, const float* gamma, float weight_scale,
+                          int training, const int32_t* surf, const void* edges_workspace, int32_t* quads, int32_t* quad_of,
+                          int64_t* faces, int64_t faces_rows);
+int kamd_flexicubes_forward(void* stream, int64_t V, int64_t C, int64_t S, int64_t num_vd, int64_t num_incidences, const float* vertices,
+                            const float* sdf, const int64_t* cube_idx, int64_t stride_cube, int64_t stride_corner, const float* beta,
+                            const float* alpha, const float* gamma, float weight_scale, const int32_t* surf, float* out_vertices,
+                            float* vd_gamma, float* l_dev);
+int kamd_flexicubes_centers(void* stream, int64_t num_vd, int64_t num_quads, const int32_t* quads, const float* vd_gamma,
+                            float* out_vertices);
+int kamd_flexicubes_backward(void* stream, int64_t V, int64_t C, int64_t S, int64_t num_vd, int64_t num_incidences, int64_t num_quads,
+                             const float* vertices, const float* sdf, const int64_t* cube_idx, int64_t stride_cube, int64_t stride_corner,
+                             const float* beta, const float* alpha, const float* gamma, float weight_scale, int training,
+                             const int32_t* surf, const int32_t* quads, const int32_t* quad_of, const float* out_vertices,
+                             const float* vd_gamma, const float* grad_vertices, const float* grad_l_dev, float* grad_x, float* grad_sdf,
+                             float* grad_beta, float* grad_alpha, float* grad_gamma);
+
+/* ------------------------------------------------------------------------- */
 /* metrics.tetmesh: tetrahedron_volume, equivolume, amips (reference: chains   */
 /* of 10-20 torch kernels, kaolin/metrics/tetmesh.py; csrc/tetmesh_metrics.hip */
 /* has the kernels).  tet_vertices (B,T,4,3): every item's (T,4,3) block is    */

@@ -467,6 +467,121 @@ def unbatched_mcube_forward_cuda(voxelgrid, iso_value):
     return verts, faces
 
 
+def _flexicubes_args(fn, vertices, scalar_field, cube_idx, beta, alpha, gamma_f):
+    """Checks before any launch -> the tensors as the kernels read them (cube_idx keeps its strides)."""
+    torch_check(isinstance(vertices, torch.Tensor) and vertices.is_cuda, f'{fn}: voxelgrid_vertices must be a CUDA tensor')
+    dev = vertices.device
+    torch_check(vertices.dim() == 2 and vertices.shape[1] == 3 and vertices.dtype == torch.float32,
+                f'{fn}: voxelgrid_vertices must be a float tensor of size {{num_vertices, 3}}')
+    V = vertices.shape[0]
+    torch_check(scalar_field.shape == (V,) and scalar_field.dtype == torch.float32 and scalar_field.device == dev,
+                f'{fn}: scalar_field must be a float tensor of size {{num_vertices}} on the device of voxelgrid_vertices')
+    torch_check(cube_idx.dim() == 2 and cube_idx.shape[1] == 8 and cube_idx.dtype == torch.int64 and cube_idx.device == dev,
+                f'{fn}: cube_idx must be a long tensor of size {{num_cubes, 8}} on the device of voxelgrid_vertices')
+    C = cube_idx.shape[0]
+    torch_check(0 < V < 2 ** 31 and 0 < 12 * C < 2 ** 31, f'{fn}: {V} vertices and {C} cubes are beyond the 32-bit ranks')
+    weights = []
+    for name, w, shape in (('beta', beta, (C, 12)), ('alpha', alpha, (C, 8)), ('gamma_f', gamma_f, (C,))):
+        torch_check(w is None or (w.shape == shape and w.dtype == torch.float32 and w.device == dev),
+                    f'{fn}: {name} must be a float tensor of size {shape} on the device of voxelgrid_vertices')
+        weights.append(None if w is None else w.detach().contiguous())
+    return vertices.detach().contiguous(), scalar_field.detach().contiguous(), cube_idx.detach(), weights
+
+
+def flexicubes_forward_cuda(vertices, scalar_field, cube_idx, resolution, weight_scale, beta=None, alpha=None, gamma_f=None,
+                            training=False):
+    """FlexiCubes on the HIP pipeline of csrc/flexicubes.hip (ours: the reference is pure PyTorch).  vertices (V, 3) and
+    scalar_field (V,) float32, cube_idx (C, 8) int64 of any strides with C = rx ry rz, raw weights beta (C, 12), alpha (C, 8),
+    gamma_f (C,) or None -> (vertices (N [+ Q], 3) float32, faces (F, 3) int64, L_dev (I,) float32, state); ``state`` is the
+    integer state ``flexicubes_backward_cuda`` needs.  An entry of cube_idx outside [0, V) raises ``IndexError`` (a flag the
+    classify kernel sets; nothing is read through such an id).  Two host reads (the sizes with the flag; the number of quads):
+    the call synchronises the current stream and cannot be captured in a graph."""
+    fn = 'flexicubes_forward_cuda'
+    x, s, cubes, (beta, alpha, gamma_f) = _flexicubes_args(fn, vertices, scalar_field, cube_idx, beta, alpha, gamma_f)
+    rx, ry, rz = (int(r) for r in resolution)
+    V, C = x.shape[0], cubes.shape[0]
+    torch_check(min(rx, ry, rz) >= 1 and rx * ry * rz == C, f'{fn}: cube_idx holds {C} cubes, not {rx} x {ry} x {rz}')
+    weight_scale, training = float(weight_scale), bool(training)
+    dev = x.device
+    lib = _lib.load()
+    sp = _lib.stream_ptr(dev)
+    grid = (_lib.ptr(s), _lib.ptr(cubes), *cubes.stride())
+    with _lib.on_device(dev):
+        ws = _lib.workspace(lib.kamd_flexicubes_workspace(C), dev)
+        host = (ctypes.c_uint32 * 9)()
+        _lib.check(lib.kamd_flexicubes_classify(sp, V, C, rx, ry, rz, *grid, _lib.ptr(ws), ctypes.cast(host, ctypes.c_void_p)), fn)
+        totals = list(host)                                    # host read 1: data-dependent sizes and the index-error flag
+        if totals[8]:
+            raise IndexError(f'{fn}: cube_idx holds an index outside [0, num_vertices = {V})')
+        S = sum(totals[0:4])
+        num_vd = sum((k + 1) * totals[k] for k in range(4))
+        num_inc = sum(totals[4:8])
+        if S == 0:
+            return (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.long, device=dev),
+                    torch.zeros((0,), dtype=torch.float32, device=dev), [])
+        surf = torch.empty((S, 4), dtype=torch.int32, device=dev)
+        ews = _lib.workspace(lib.kamd_flexicubes_edges_workspace(S), dev)
+        nq = ctypes.c_int64(0)
+        _lib.check(lib.kamd_flexicubes_edges(sp, V, C, S, *grid, _lib.ptr(ws), _lib.ptr(surf), _lib.ptr(ews),
+                                             ctypes.cast(ctypes.byref(nq), ctypes.c_void_p)), fn)
+        Q = int(nq.value)                                      # host read 2
+        verts = torch.empty((num_vd + (Q if training else 0), 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((Q * (4 if training else 2), 3), dtype=torch.long, device=dev)
+        l_dev = torch.empty((num_inc,), dtype=torch.float32, device=dev)
+        vd_gamma = torch.empty((num_vd,), dtype=torch.float32, device=dev)
+        quads = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+        quad_of = torch.empty((12 * S,), dtype=torch.int32, device=dev)
+        if Q > 0:
+            _lib.check(lib.kamd_flexicubes_faces(sp, C, S, num_vd, Q, _lib.ptr(gamma_f), weight_scale, int(training), _lib.ptr(surf),
+                                                 _lib.ptr(ews), _lib.ptr(quads), _lib.ptr(quad_of), _lib.ptr(faces), faces.shape[0]),
+                       fn)
+        _lib.check(lib.kamd_flexicubes_forward(sp, V, C, S, num_vd, num_inc, _lib.ptr(x), *grid, _lib.ptr(beta), _lib.ptr(alpha),
+                                               _lib.ptr(gamma_f), weight_scale, _lib.ptr(surf), _lib.ptr(verts), _lib.ptr(vd_gamma),
+                                               _lib.ptr(l_dev)), fn)
+        if training and Q > 0:
+            _lib.check(lib.kamd_flexicubes_centers(sp, num_vd, Q, _lib.ptr(quads), _lib.ptr(vd_gamma), _lib.ptr(verts)), fn)
+    return verts, faces, l_dev, [surf, quads, quad_of, vd_gamma]
+
+
+def flexicubes_backward_cuda(grad_vertices, grad_l_dev, vertices, scalar_field, cube_idx, weight_scale, beta, alpha, gamma_f, training,
+                             out_vertices, state):
+    """The cotangents of the two float results of ``flexicubes_forward_cuda``, its inputs, its vertices and its state -> the
+    gradients of (vertices, scalar_field, beta, alpha, gamma_f), None for a weight that is None (and for gamma_f without training:
+    it only picks the split).  One launch, one thread per surface cube, recomputing from the inputs; the rows of the weights are
+    written by their owner, the shared grid vertices and sdf values take float atomic adds."""
+    fn = 'flexicubes_backward_cuda'
+    x, s, cubes, (beta, alpha, gamma_f) = _flexicubes_args(fn, vertices, scalar_field, cube_idx, beta, alpha, gamma_f)
+    dev = x.device
+    V, C = x.shape[0], cubes.shape[0]
+    training = bool(training)
+    gx, gs = torch.zeros_like(x), torch.zeros_like(s)
+    gb = None if beta is None else torch.zeros_like(beta)
+    ga = None if alpha is None else torch.zeros_like(alpha)
+    gg = None if gamma_f is None or not training else torch.zeros_like(gamma_f)
+    if len(state) == 0:                                        # an empty surface
+        return gx, gs, gb, ga, gg
+    surf, quads, quad_of, vd_gamma = state
+    S, Q, num_vd = surf.shape[0], quads.shape[0], vd_gamma.shape[0]
+    torch_check(surf.shape == (S, 4) and quads.shape == (Q, 4) and quad_of.shape == (12 * S,) and
+                all(t.dtype == torch.int32 and t.device == dev and t.is_contiguous() for t in (surf, quads, quad_of)) and
+                vd_gamma.dtype == torch.float32 and vd_gamma.device == dev, f'{fn}: state is not the state of a forward call')
+    out = out_vertices.detach()
+    torch_check(out.shape == (num_vd + (Q if training else 0), 3) and out.dtype == torch.float32 and out.device == dev
+                and out.is_contiguous(), f'{fn}: out_vertices are not the vertices of that forward call')
+    torch_check(grad_vertices.shape == out.shape and grad_vertices.device == dev and grad_l_dev.dim() == 1
+                and grad_l_dev.device == dev, f'{fn}: the cotangents must have the shapes of vertices and L_dev')
+    gv = grad_vertices.detach().float().contiguous()
+    gl = grad_l_dev.detach().float().contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        _lib.check(lib.kamd_flexicubes_backward(_lib.stream_ptr(dev), V, C, S, num_vd, gl.shape[0], Q, _lib.ptr(x), _lib.ptr(s),
+                                                _lib.ptr(cubes), *cubes.stride(), _lib.ptr(beta), _lib.ptr(alpha), _lib.ptr(gamma_f),
+                                                float(weight_scale), int(training), _lib.ptr(surf), _lib.ptr(quads),
+                                                _lib.ptr(quad_of), _lib.ptr(out), _lib.ptr(vd_gamma), _lib.ptr(gv), _lib.ptr(gl),
+                                                _lib.ptr(gx), _lib.ptr(gs), _lib.ptr(gb), _lib.ptr(ga), _lib.ptr(gg)), fn)
+    return gx, gs, gb, ga, gg
+
+
 def check_tets_in_range(tets, num_vertices, fn='marching_tetrahedra'):
     """tets (T, 4) of an integer dtype on any device: raises IndexError when an entry lies outside [0, num_vertices).  Pure
     torch (one min / max pass and one host read); called before any kernel sees the ids -- an id out of range would make the
@@ -1935,6 +2050,8 @@ conversions = _types.SimpleNamespace(mesh_to_spc_cuda=mesh_to_spc_cuda, marching
                                      voxelgrids_to_trianglemeshes_cuda=voxelgrids_to_trianglemeshes_cuda,
                                      unbatched_mcube_forward_cuda=unbatched_mcube_forward_cuda,
                                      mcube_forward_cuda=mcube_forward_cuda, mcube_backward_cuda=mcube_backward_cuda,
+                                     flexicubes_forward_cuda=flexicubes_forward_cuda,
+                                     flexicubes_backward_cuda=flexicubes_backward_cuda,
                                      gs_to_spc_cuda=gs_to_spc_cuda, integrate_gs_cuda=integrate_gs_cuda,
                                      pointcloud_to_spc_cuda=pointcloud_to_spc_cuda,
                                      pointclouds_to_voxelgrids_cuda=pointclouds_to_voxelgrids_cuda)

@@ -7,6 +7,7 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
     kaolin_amd.ops.conversions  trianglemeshes_to_voxelgrids, marching_tetrahedra (HIP extraction pipeline),
                                 voxelgrids_to_cubic_meshes (sort-free HIP pipeline), voxelgrids_to_trianglemeshes (marching
                                 cubes: batched, differentiable HIP pipeline over a generated case table), pointclouds_to_voxelgrids,
+                                FlexiCubes (differentiable dual marching cubes: HIP pipeline, forward and backward),
                                 unbatched_pointcloud_to_spc (HIP pair sort + atomic-free segmented mean)
     kaolin_amd.ops.mesh         subdivide_tetmesh (HIP edge-midpoint pipeline), inverse_vertices_offset, check_sign,
                                 subdivide_trianglemesh (Loop subdivision with a per-vertex alpha, HIP pipeline),

@@ -183,6 +183,18 @@ for _t in ('u8', 'f16', 'f32'):
     SIGNATURES[f'kamd_mcube_emit_vertices_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _f, _vp, _vp, _i64])
 for _t in ('f16', 'f32'):
     SIGNATURES[f'kamd_mcube_backward_{_t}'] = (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i64, _i64, _i64, _f, _vp, _vp, _i64, _vp])
+SIGNATURES.update({
+    'kamd_flexicubes_workspace': (_sz, [_i64]),
+    'kamd_flexicubes_classify': (_i, [_vp, _i64, _i64, _i, _i, _i, _vp, _vp, _i64, _i64, _vp, _vp]),
+    'kamd_flexicubes_edges_workspace': (_sz, [_i64]),
+    'kamd_flexicubes_edges': (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'kamd_flexicubes_faces': (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
+    'kamd_flexicubes_forward': (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f, _vp, _vp, _vp,
+                                     _vp]),
+    'kamd_flexicubes_centers': (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    'kamd_flexicubes_backward': (_i, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _f, _i,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+})
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_marching_tetrahedra_classify_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp])
     SIGNATURES[f'kamd_marching_tetrahedra_emit_{_t}'] = (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp])

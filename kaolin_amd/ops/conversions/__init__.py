@@ -8,3 +8,5 @@ from .gaussians import gs_to_voxelgrid  # noqa: F401
 from . import gaussians  # noqa: F401
 from .pointcloud import pointclouds_to_voxelgrids, unbatched_pointcloud_to_spc  # noqa: F401
 from . import pointcloud  # noqa: F401
+from .flexicubes import FlexiCubes  # noqa: F401
+from . import flexicubes  # noqa: F401

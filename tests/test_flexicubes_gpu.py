@@ -1,0 +1,234 @@
+"""ops.conversions.FlexiCubes on the GPU: the HIP pipeline (csrc/flexicubes.hip) against the reference's recorded results and against
+the torch formulation on the same GPU tensors -- integers equal, floats within the bound of test_flexicubes_cpu.py against the
+formulation in float64 -- at the sizes where the pipeline takes another path."""
+import pytest
+import torch
+
+from kaolin_amd import _C
+from kaolin_amd.ops.conversions import FlexiCubes
+from kaolin_amd.ops.conversions.flexicubes import flexicubes as fcm
+from test_flexicubes_cpu import (U, WS, assert_close, bounds, case_inputs, check_case, check_cases256, check_forward, check_grads,
+                                 forward_cases, golden_grads, grads_of, settle_cotangent, tensor, term_sums)
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+
+
+def hip_call(v, s, c, res, beta, alpha, gamma, training):
+    """The public call on the GPU; the HIP path takes it (float32, no features)."""
+    move = [None if t is None else t.to(DEV) for t in (v, s, c, beta, alpha, gamma)]
+    return FlexiCubes(DEV)(move[0], move[1], move[2], list(res), beta=move[3], alpha=move[4], gamma_f=move[5], training=training)
+
+
+def formulation(inputs, training, dtype):
+    """The torch formulation on the GPU -> (vertices, faces, L_dev)."""
+    v, s, c, res, beta, alpha, gamma = inputs
+    cast = [None if t is None else t.to(device=DEV, dtype=dtype) for t in (v, s, beta, alpha, gamma)]
+    return fcm.flexicubes_torch(cast[0], cast[1], c.to(DEV), res, WS, cast[2], cast[3], cast[4], training)[:3]
+
+
+def make_grid(res, seed, kind='sphere', weights=True):
+    """CPU inputs: a jittered grid and an sdf -- 'sphere' (plus noise: cubes of several dual vertices), 'signs' (random signs:
+    every cube is a surface cube, all four count classes) or 'plane' (exactly the middle layer of cubes along z is crossed)."""
+    g = torch.Generator().manual_seed(seed)
+    v, c = FlexiCubes('cpu').construct_voxel_grid(res)
+    res = fcm._resolution3(res)
+    cell = 1.0 / torch.tensor(res, dtype=torch.float32)
+    v = v + (torch.rand(v.shape, generator=g) - 0.5) * 0.2 * cell
+    if kind == 'sphere':
+        s = (v - torch.tensor([0.04, -0.03, 0.02])).norm(dim=-1) - 0.33 + 0.3 * float(cell.max()) * torch.randn(v.shape[0], generator=g)
+    elif kind == 'signs':
+        s = torch.where(torch.rand(v.shape[0], generator=g) < 0.5, -1.0, 1.0) * (0.25 + 0.75 * torch.rand(v.shape[0], generator=g))
+    else:
+        layer = torch.round((v[:, 2] + 0.5) * res[2])
+        s = torch.where(layer <= res[2] // 2, -1.0, 1.0) * (0.25 + 0.75 * torch.rand(v.shape[0], generator=g))
+    n = c.shape[0]
+    if not weights:
+        return v, s, c, res, None, None, None
+    return v, s, c, res, 0.5 * torch.randn(n, 12, generator=g), 0.5 * torch.randn(n, 8, generator=g), 0.5 * torch.randn(n, generator=g)
+
+
+def check_against_formulation(inputs, training, what, got=None):
+    got = hip_call(*inputs, training) if got is None else got
+    same = formulation(inputs, training, torch.float32)
+    want = formulation(inputs, training, torch.float64)
+    assert got[0].dtype == torch.float32 and got[2].dtype == torch.float32 and got[1].dtype == torch.long
+    assert torch.equal(same[1], want[1]), f'{what}: the inputs leave the quad split to rounding'
+    num_vd = want[0].shape[0] - (want[1].shape[0] // 4 if training else 0)
+    check_forward(got, want[0].cpu(), want[2].cpu(), same[1].cpu(), inputs, num_vd, what)
+    return got
+
+
+def test_cases256():
+    check_cases256(hip_call)
+
+
+@pytest.mark.parametrize('case,training', forward_cases())
+def test_golden_forward(case, training):
+    check_case(hip_call, case, training)
+
+
+@pytest.mark.parametrize('name', ['empty_pos', 'empty_neg'])
+def test_empty_surface(name):
+    inputs = case_inputs(name)
+    got = hip_call(*inputs, True)
+    assert got[0].shape == (0, 3) and got[1].shape == (0, 3) and got[2].shape == (0,)
+    assert got[0].dtype == torch.float32 and got[1].dtype == torch.long and got[0].device.type == 'cuda'
+    leaves = [t.clone().to(DEV).requires_grad_() for t in inputs[:2]]
+    out = FlexiCubes(DEV)(leaves[0], leaves[1], inputs[2].to(DEV), 2)
+    (out[0].sum() + out[2].sum()).backward()
+    assert not bool(leaves[0].grad.any()) and not bool(leaves[1].grad.any())
+
+
+# resolution 1; 1023 / 1024 / 1025 cubes (the count scan's block) and 1331; the same counts of surface cubes ('plane': 12 S pairs
+# around the 1024-scan of the runs); 170 / 171 surface cubes (2040 / 2052 pairs: the sort's block of 2048); 'signs': every cube
+# a surface cube, all four count classes, incidence counts that differ from lane to lane across wavefronts and workgroups
+SHAPES = [((1, 1, 1), 'signs'), ((33, 31, 1), 'sphere'), ((32, 8, 4), 'sphere'), ((41, 25, 1), 'sphere'), ((11, 11, 11), 'sphere'),
+          ((33, 31, 3), 'plane'), ((32, 32, 3), 'plane'), ((41, 25, 3), 'plane'), ((17, 10, 3), 'plane'), ((19, 9, 3), 'plane'),
+          ((8, 8, 5), 'signs'), ((7, 9, 6), 'signs')]
+
+
+@pytest.mark.parametrize('training', [False, True])
+@pytest.mark.parametrize('res,kind', SHAPES, ids=lambda p: 'x'.join(map(str, p)) if isinstance(p, tuple) else p)
+def test_against_formulation(res, kind, training):
+    inputs = make_grid(res, 100 + sum(res), kind)
+    if kind == 'plane':
+        topo = fcm.topology_torch(inputs[1], inputs[2], inputs[3])
+        assert topo['cubes'].shape[0] == res[0] * res[1]
+    got = check_against_formulation(inputs, training, f'{res} {kind}')
+    if kind == 'signs' and res != (1, 1, 1):
+        assert got[1].shape[0] > 0
+
+
+@pytest.mark.parametrize('training', [False, True])
+def test_none_defaults(training):
+    inputs = make_grid((6, 5, 7), 7, 'sphere', weights=False)
+    check_against_formulation(inputs, training, 'defaults')
+    v, s, c, res = inputs[:4]
+    got = FlexiCubes(DEV)(v.to(DEV), s.to(DEV), c.to(DEV), list(res))     # every default of the signature
+    check_against_formulation(inputs, False, 'signature defaults', got)
+
+
+def test_sparse_vertex_ids():
+    """Vertex ids mapped sparsely into [0, 70 001): 17 bits per half of the key, one more pass of the sort per half."""
+    v, s, c, res, beta, alpha, gamma = make_grid((6, 7, 5), 11, 'sphere')
+    g = torch.Generator().manual_seed(12)
+    ids = torch.randperm(70000, generator=g)[:v.shape[0]]
+    ids[int(c[c.shape[0] // 2, 3])] = 70000
+    big_v, big_s = torch.zeros(70001, 3), torch.full((70001,), -1.0)
+    big_v[ids], big_s[ids] = v, s
+    inputs = (big_v, big_s, ids[c], res, beta, alpha, gamma)
+    sparse = check_against_formulation(inputs, True, 'sparse ids')
+    dense = hip_call(v, s, c, res, beta, alpha, gamma, True)
+    assert sparse[0].shape == dense[0].shape and sparse[1].shape == dense[1].shape
+
+
+def test_cube_idx_strides():
+    inputs = make_grid((5, 6, 4), 13, 'sphere')
+    v, s, c, res, beta, alpha, gamma = inputs
+    want = hip_call(*inputs, True)
+    transposed = c.to(DEV).t().contiguous().t()                            # strides (1, C)
+    wide = torch.full((c.shape[0], 19), -5, dtype=torch.long, device=DEV)
+    wide[:, 3::2] = c.to(DEV)                                              # strides (19, 2)
+    for cubes in (transposed, wide[:, 3::2]):
+        assert not cubes.is_contiguous()
+        got = FlexiCubes(DEV)(v.to(DEV), s.to(DEV), cubes, list(res), beta=beta.to(DEV), alpha=alpha.to(DEV), gamma_f=gamma.to(DEV),
+                              training=True)
+        for a, b in zip(got, want):
+            assert torch.equal(a, b)
+
+
+def test_index_out_of_range_is_an_index_error():
+    """A flagged check, not a fault: the classify kernel compares every id with V before it reads through it."""
+    inputs = make_grid((4, 4, 4), 17, 'sphere')
+    v, s, c, res, beta, alpha, gamma = inputs
+    for bad in (v.shape[0], -1, 2 ** 40):
+        broken = c.clone()
+        broken[37, 5] = bad
+        with pytest.raises(IndexError, match='cube_idx'):
+            hip_call(v, s, broken, res, beta, alpha, gamma, False)
+        check_against_formulation(inputs, False, 'after the IndexError')
+
+
+def test_two_calls_give_the_same_bits():
+    inputs = make_grid((12, 11, 13), 19, 'sphere')
+    for training in (False, True):
+        a, b = hip_call(*inputs, training), hip_call(*inputs, training)
+        for x, y in zip(a, b):
+            assert torch.equal(x, y)
+
+
+def test_second_round_of_the_count_scan():
+    """More than 8192 workgroups of cubes: the count scan's second round."""
+    res = (129, 128, 128)
+    g = torch.Generator().manual_seed(23)
+    v, c = FlexiCubes(DEV).construct_voxel_grid(res)
+    s = (v - torch.tensor([0.04, -0.03, 0.02], device=DEV)).norm(dim=-1) - 0.33
+    gamma = torch.randn(c.shape[0], generator=g).to(DEV)
+    got = FlexiCubes(DEV)(v, s, c, list(res), gamma_f=gamma, training=True)
+    want = fcm.flexicubes_torch(v.double(), s.double(), c, res, WS, None, None, gamma.double(), True)
+    assert got[1].shape[0] > 100000
+    num_vd = want[0].shape[0] - want[1].shape[0] // 4
+    check_forward(got, want[0].cpu(), want[2].cpu(), want[1].cpu(), (v, s, c, res, None, None, gamma), num_vd, '129 x 128 x 128')
+
+
+def hip_fn(v, s, c, res, beta, alpha, gamma, training):
+    return FlexiCubes(DEV)(v, s, c, list(res), beta=beta, alpha=alpha, gamma_f=gamma, training=training)
+
+
+def test_golden_grads():
+    inputs = case_inputs('grid')
+    cot_v, cot_l = tensor('grads_cot_verts'), tensor('grads_cot_ldev')
+    got = grads_of(hip_fn, inputs, cot_v, cot_l, torch.float32, DEV)
+    check_grads(got, golden_grads('f64'), inputs, cot_v, cot_l, 'hip golden')
+
+
+@pytest.mark.parametrize('res,kind', [((9, 8, 7), 'sphere'), ((6, 5, 4), 'signs'), ((17, 10, 3), 'plane')],
+                         ids=lambda p: 'x'.join(map(str, p)) if isinstance(p, tuple) else p)
+def test_backward_against_float64_autograd(res, kind):
+    inputs = make_grid(res, 200 + sum(res), kind)
+    out = formulation(inputs, True, torch.float64)
+    g = torch.Generator().manual_seed(29)
+    cot_v = (torch.rand(out[0].shape, generator=g) * 2 - 1).float()
+    cot_l = settle_cotangent((torch.rand(out[2].shape, generator=g) * 2 - 1).float(), out[2], inputs)
+
+    def formulation_fn(v, s, c, r, beta, alpha, gamma, training):
+        return fcm.flexicubes_torch(v, s, c, r, WS, beta, alpha, gamma, training)[:3]
+    want = grads_of(formulation_fn, inputs, cot_v, cot_l, torch.float64, DEV)
+    got = grads_of(hip_fn, inputs, cot_v, cot_l, torch.float32, DEV)
+    check_grads(got, {k: w.cpu() for k, w in want.items()}, inputs, cot_v, cot_l, f'hip {res} {kind}')
+
+
+def test_backward_without_weights_and_without_training():
+    v, s, c, res = make_grid((7, 6, 5), 31, 'sphere', weights=False)[:4]
+    inputs = (v, s, c, res, None, None, None)
+    g = torch.Generator().manual_seed(37)
+    gamma = 0.5 * torch.randn(c.shape[0], generator=g)
+    out64 = formulation(inputs, False, torch.float64)
+    cot_v, cot_l = torch.ones(out64[0].shape), settle_cotangent(torch.ones(out64[2].shape), out64[2], inputs)
+    grads = {}
+    for name, dtype, fn in (('hip', torch.float32, hip_fn),
+                            ('want', torch.float64, lambda *a: fcm.flexicubes_torch(a[0], a[1], a[2], a[3], WS, a[4], a[5], a[6], a[7])[:3])):
+        leaves = [t.clone().to(device=DEV, dtype=dtype).requires_grad_() for t in (v, s, gamma)]
+        out = fn(leaves[0], leaves[1], c.to(DEV), res, None, None, leaves[2], False)
+        (out[0].sum() + (out[2] * cot_l.to(device=DEV, dtype=dtype)).sum()).backward()
+        assert leaves[2].grad is None                                      # gamma_f only picks the split
+        grads[name] = dict(vertices=leaves[0].grad, sdf=leaves[1].grad)
+    T, amp = term_sums(inputs, cot_v, cot_l, training=False)
+    n_c = bounds(v, None, None, None)[1]
+    for name in ('vertices', 'sdf'):
+        want = grads['want'][name].cpu()
+        assert_close(grads['hip'][name], want, (2 * n_c + 60) * U * amp * T[name] + U * want.abs() + 1e-300, f'no weights grad {name}')
+
+
+def test_operator_checks_its_arguments():
+    v, s, c, res, beta, alpha, gamma = [t.to(DEV) if torch.is_tensor(t) else t for t in make_grid((3, 3, 3), 41, 'sphere')]
+    op = _C.ops.conversions.flexicubes_forward_cuda
+    with pytest.raises(RuntimeError, match='cubes'):
+        op(v, s, c[:-1], res, WS)
+    with pytest.raises(RuntimeError, match='scalar_field'):
+        op(v, s[:-1], c, res, WS)
+    with pytest.raises(RuntimeError, match='beta'):
+        op(v, s, c, res, WS, beta=beta[:, :11])
+    with pytest.raises(RuntimeError, match='voxelgrid_vertices'):
+        op(v.double(), s, c, res, WS)
