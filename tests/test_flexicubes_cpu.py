@@ -19,6 +19,7 @@ INPUTS of a case in float64, never from a result under test):
                 Precondition on the inputs (asserted): every L_dev with a cotangent other than 0 exceeds its own bound, so that
                 its derivative sign(dist - mean) is settled (settle_cotangent zeroes the others)
 The reference's own float32 results must pass the same bounds against its float64 results (test_reference_float32_passes_the_bound).
+The gradients are judged a second time by the per-term bound of flexicubes_gradient_oracle.py (local conditioning factors).
 """
 import os
 import subprocess
@@ -28,6 +29,7 @@ import numpy as np
 import pytest
 import torch
 
+import flexicubes_gradient_oracle as oracle
 from kaolin_amd.ops.conversions import FlexiCubes
 from kaolin_amd.ops.conversions.flexicubes import flexicubes as fcm
 
@@ -314,7 +316,9 @@ def test_golden_grads():
     got64 = grads_of(torch_call, inputs, cot_v, cot_l, torch.float64)
     for name, want in golden_grads('f64').items():
         assert torch.allclose(got64[name], want, rtol=1e-9, atol=1e-12), name
-    check_grads(grads_of(torch_call, inputs, cot_v, cot_l, torch.float32), golden_grads('f64'), inputs, cot_v, cot_l, 'torch f32')
+    got32 = grads_of(torch_call, inputs, cot_v, cot_l, torch.float32)
+    check_grads(got32, golden_grads('f64'), inputs, cot_v, cot_l, 'torch f32')
+    oracle.check_grads_local(got32, golden_grads('f64'), inputs, cot_v, cot_l, True, 'torch f32')
 
 
 def test_reference_float32_passes_the_bound():
@@ -334,6 +338,8 @@ def test_reference_float32_passes_the_bound():
     check_cases256(stored)
     check_grads(golden_grads('f32'), golden_grads('f64'), case_inputs('grid'), tensor('grads_cot_verts'), tensor('grads_cot_ldev'),
                 'reference f32')
+    oracle.check_grads_local(golden_grads('f32'), golden_grads('f64'), case_inputs('grid'), tensor('grads_cot_verts'),
+                             tensor('grads_cot_ldev'), True, 'reference f32')
 
 
 def test_half_runs():

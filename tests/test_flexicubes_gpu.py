@@ -4,6 +4,8 @@ formulation in float64 -- at the sizes where the pipeline takes another path."""
 import pytest
 import torch
 
+import flexicubes_gradient_oracle as oracle
+from flexicubes_boundary_cases import make_grid
 from kaolin_amd import _C
 from kaolin_amd.ops.conversions import FlexiCubes
 from kaolin_amd.ops.conversions.flexicubes import flexicubes as fcm
@@ -25,27 +27,6 @@ def formulation(inputs, training, dtype):
     v, s, c, res, beta, alpha, gamma = inputs
     cast = [None if t is None else t.to(device=DEV, dtype=dtype) for t in (v, s, beta, alpha, gamma)]
     return fcm.flexicubes_torch(cast[0], cast[1], c.to(DEV), res, WS, cast[2], cast[3], cast[4], training)[:3]
-
-
-def make_grid(res, seed, kind='sphere', weights=True):
-    """CPU inputs: a jittered grid and an sdf -- 'sphere' (plus noise: cubes of several dual vertices), 'signs' (random signs:
-    every cube is a surface cube, all four count classes) or 'plane' (exactly the middle layer of cubes along z is crossed)."""
-    g = torch.Generator().manual_seed(seed)
-    v, c = FlexiCubes('cpu').construct_voxel_grid(res)
-    res = fcm._resolution3(res)
-    cell = 1.0 / torch.tensor(res, dtype=torch.float32)
-    v = v + (torch.rand(v.shape, generator=g) - 0.5) * 0.2 * cell
-    if kind == 'sphere':
-        s = (v - torch.tensor([0.04, -0.03, 0.02])).norm(dim=-1) - 0.33 + 0.3 * float(cell.max()) * torch.randn(v.shape[0], generator=g)
-    elif kind == 'signs':
-        s = torch.where(torch.rand(v.shape[0], generator=g) < 0.5, -1.0, 1.0) * (0.25 + 0.75 * torch.rand(v.shape[0], generator=g))
-    else:
-        layer = torch.round((v[:, 2] + 0.5) * res[2])
-        s = torch.where(layer <= res[2] // 2, -1.0, 1.0) * (0.25 + 0.75 * torch.rand(v.shape[0], generator=g))
-    n = c.shape[0]
-    if not weights:
-        return v, s, c, res, None, None, None
-    return v, s, c, res, 0.5 * torch.randn(n, 12, generator=g), 0.5 * torch.randn(n, 8, generator=g), 0.5 * torch.randn(n, generator=g)
 
 
 def check_against_formulation(inputs, training, what, got=None):
@@ -181,6 +162,7 @@ def test_golden_grads():
     cot_v, cot_l = tensor('grads_cot_verts'), tensor('grads_cot_ldev')
     got = grads_of(hip_fn, inputs, cot_v, cot_l, torch.float32, DEV)
     check_grads(got, golden_grads('f64'), inputs, cot_v, cot_l, 'hip golden')
+    oracle.check_grads_local(got, golden_grads('f64'), inputs, cot_v, cot_l, True, 'hip golden')
 
 
 @pytest.mark.parametrize('res,kind', [((9, 8, 7), 'sphere'), ((6, 5, 4), 'signs'), ((17, 10, 3), 'plane')],
@@ -197,6 +179,7 @@ def test_backward_against_float64_autograd(res, kind):
     want = grads_of(formulation_fn, inputs, cot_v, cot_l, torch.float64, DEV)
     got = grads_of(hip_fn, inputs, cot_v, cot_l, torch.float32, DEV)
     check_grads(got, {k: w.cpu() for k, w in want.items()}, inputs, cot_v, cot_l, f'hip {res} {kind}')
+    oracle.check_grads_local(got, {k: w.cpu() for k, w in want.items()}, inputs, cot_v, cot_l, True, f'hip {res} {kind}')
 
 
 def test_backward_without_weights_and_without_training():
@@ -219,6 +202,7 @@ def test_backward_without_weights_and_without_training():
     for name in ('vertices', 'sdf'):
         want = grads['want'][name].cpu()
         assert_close(grads['hip'][name], want, (2 * n_c + 60) * U * amp * T[name] + U * want.abs() + 1e-300, f'no weights grad {name}')
+    oracle.check_grads_local(grads['hip'], {k: w.cpu() for k, w in grads['want'].items()}, inputs, cot_v, cot_l, False, 'no weights')
 
 
 def test_operator_checks_its_arguments():
