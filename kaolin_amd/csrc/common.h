@@ -20,6 +20,8 @@
   } while (0)
 
 static inline int kamd_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// the parts of a workspace start at multiples of 16 bytes
+static inline size_t kamd_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // ---- atomics ---------------------------------------------------------------
 // fp32/fp64 global atomic add are single hardware instructions on gfx950

@@ -15,8 +15,9 @@
 //                           around it through the input's strides.  Writes one code byte per point -- bits 0..2 face of axis d,
 //                           3..5 inverted, 6 vertex -- and four counts per workgroup (vertices, faces of axis 0, 1, 2) from
 //                           __ballot / __popcll and an LDS sum.  A workgroup never straddles two items.  No atomics.
-//   2. cm_scan_kernel       one workgroup per (item, counter): exclusive scan of the workgroup counts in place, the total of the
-//                           row beside it.  cm_bases_kernel: the int64 prefix over the items of the vertex and quad totals.
+//   2. rows_scan_kernel     (count_scan.h) one workgroup per (item, counter): exclusive scan of the workgroup counts in place,
+//                           the total of the row beside it.  bases_kernel<4>: the int64 prefix over the items of the vertex
+//                           and quad totals.
 //      The host reads the B x 4 totals (ONE synchronising copy for the whole batch) and allocates the outputs.
 //   3. cm_vertices_kernel   rank = workgroup offset + ballot prefix inside the workgroup; writes the float3 and the rank into an
 //                           int32 array over the lattice (only at the vertices: nothing else is ever gathered).
@@ -26,6 +27,7 @@
 // All four read the code byte, so the counts of step 1 and the ranks of steps 3 and 4 agree whatever the values (NaN included).
 // Everything is a plain store at an index computed from prefix counts: bit-identical run to run, on any stream.
 #include "common.h"
+#include "count_scan.h"
 #include "profile.h"
 #include "../../include/kaolin_amd.h"
 
@@ -33,22 +35,12 @@ namespace {
 
 constexpr int CM_THREADS = 256;
 constexpr int CM_WAVES = CM_THREADS / 64;
-constexpr int CM_SCAN_THREADS = 1024;
-constexpr int CM_SCAN_ITEMS = 8;  // consecutive counts per thread and round of the scan
-
-struct cm_half {
-  unsigned short bits;
-};
-__device__ __forceinline__ float cm_value(unsigned char v) { return (float)v; }
-__device__ __forceinline__ float cm_value(float v) { return v; }
-__device__ __forceinline__ float cm_value(cm_half v) { return __half2float(__ushort_as_half(v.bits)); }
 
 // the workspace: [totals B x 4 u32][bases B x 2 i64][counts B x 4 x G u32][ranks B x L i32][codes B x L u8], 16-byte aligned parts
 struct CmLayout {
   long long L, G, blocks;  // lattice points and workgroups per item; workgroups of the batch
   size_t totals, bases, counts, ranks, codes, bytes;
 };
-inline size_t cm_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 // false: nothing to do (an empty batch) or a lattice the 32-bit indices do not cover
 bool cm_layout(long long B, int X, int Y, int Z, CmLayout* lay) {
   if (B <= 0 || X < 0 || Y < 0 || Z < 0) return false;
@@ -60,31 +52,21 @@ bool cm_layout(long long B, int X, int Y, int Z, CmLayout* lay) {
   if (B > lim / (lay->G > 4 ? lay->G : 4)) return false;  // (the grids: B G and B x 4 workgroups)
   lay->blocks = B * lay->G;
   size_t o = 0;
-  lay->totals = o, o += cm_align16((size_t)B * 4 * 4);
-  lay->bases = o, o += cm_align16((size_t)B * 2 * 8);
-  lay->counts = o, o += cm_align16((size_t)B * 4 * (size_t)lay->G * 4);
-  lay->ranks = o, o += cm_align16((size_t)B * (size_t)lay->L * 4);
-  lay->codes = o, o += cm_align16((size_t)B * (size_t)lay->L);
+  lay->totals = o, o += kamd_align16((size_t)B * 4 * 4);
+  lay->bases = o, o += kamd_align16((size_t)B * 2 * 8);
+  lay->counts = o, o += kamd_align16((size_t)B * 4 * (size_t)lay->G * 4);
+  lay->ranks = o, o += kamd_align16((size_t)B * (size_t)lay->L * 4);
+  lay->codes = o, o += kamd_align16((size_t)B * (size_t)lay->L);
   lay->bytes = o;
   return true;
-}
-
-unsigned cm_grid(long long blocks) {
-  const long long cap = (long long)KAMD_NUM_CU * 32;
-  return (unsigned)(blocks < cap ? blocks : cap);
 }
 
 // the number of set flags in the threads before this one of the workgroup (s_waves: CM_WAVES words per flag, synchronised here)
 template <int NF>
 __device__ __forceinline__ void cm_block_prefix(const bool (&flag)[NF], unsigned (&prefix)[NF], unsigned (*s_waves)[CM_WAVES]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const int wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    const unsigned long long m = __ballot(flag[f]);
-    prefix[f] = (unsigned)__popcll(m & below);
-    if (lane == 0) s_waves[f][wave] = (unsigned)__popcll(m);
-  }
+  for (int f = 0; f < NF; ++f) prefix[f] = ballot_prefix<1>(flag[f] ? 1u : 0u, &s_waves[f][wave]);
   __syncthreads();
 #pragma unroll
   for (int f = 0; f < NF; ++f)
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(CM_THREADS) void cm_classify_kernel(const T* __rest
           for (int c = 0; c < 2; ++c) {
             const int x = i - 1 + a, y = j - 1 + b, z = k - 1 + c;
             v[a][b][c] = 0.f;
-            if (x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z) v[a][b][c] = cm_value(src[x * sx + y * sy + z * sz]);
+            if (x >= 0 && x < X && y >= 0 && y < Y && z >= 0 && z < Z) v[a][b][c] = grid_value(src[x * sx + y * sy + z * sz]);
           }
       bool any = false;
 #pragma unroll
@@ -146,86 +128,6 @@ __global__ __launch_bounds__(CM_THREADS) void cm_classify_kernel(const T* __rest
       counts[(item * 4 + threadIdx.x) * G + g] = sum;
     }
     __syncthreads();  // (s_waves is rewritten by the next round)
-  }
-}
-
-// exclusive scan of one value per thread over the workgroup; `total` = the sum.  s_w: (threads / 64 + 1) words.
-template <typename V>
-__device__ __forceinline__ V cm_block_exscan(V v, V* s_w, V* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  V incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const V o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    const V w = lane < nw ? s_w[lane] : (V)0;
-    V wi = w;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const V o = __shfl_up(wi, d);
-      if (lane >= d) wi += o;
-    }
-    if (lane < nw) s_w[lane] = wi - w;
-    if (lane == nw - 1) s_w[nw] = wi;
-  }
-  __syncthreads();
-  const V res = s_w[wave] + incl - v;
-  *total = s_w[nw];
-  __syncthreads();  // (s_w is rewritten by the next round)
-  return res;
-}
-
-// row = one counter of one item: counts[row * G .. + G) <- its exclusive scan, totals[row] <- its sum (< 2^31)
-__global__ __launch_bounds__(CM_SCAN_THREADS) void cm_scan_kernel(long long G, unsigned* __restrict__ counts,
-                                                                  unsigned* __restrict__ totals) {
-  __shared__ unsigned s_w[CM_SCAN_THREADS / 64 + 1];
-  unsigned* row = counts + (long long)blockIdx.x * G;
-  unsigned carry = 0u;
-  for (long long base = 0; base < G; base += CM_SCAN_THREADS * CM_SCAN_ITEMS) {
-    const long long first = base + (long long)threadIdx.x * CM_SCAN_ITEMS;
-    unsigned c[CM_SCAN_ITEMS], sum = 0u;
-#pragma unroll
-    for (int e = 0; e < CM_SCAN_ITEMS; ++e) {
-      c[e] = first + e < G ? row[first + e] : 0u;
-      sum += c[e];
-    }
-    unsigned total;
-    unsigned run = carry + cm_block_exscan(sum, s_w, &total);
-#pragma unroll
-    for (int e = 0; e < CM_SCAN_ITEMS; ++e) {
-      if (first + e < G) row[first + e] = run;
-      run += c[e];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
-
-// bases[2 b], bases[2 b + 1] <- the vertices and the quads of the items before b (int64: the batch may exceed 2^31 rows)
-__global__ __launch_bounds__(CM_THREADS) void cm_bases_kernel(long long B, const unsigned* __restrict__ totals,
-                                                              long long* __restrict__ bases) {
-  __shared__ long long s_w[CM_WAVES + 1];
-  long long carry_v = 0, carry_q = 0;
-  for (long long base = 0; base < B; base += CM_THREADS) {
-    const long long b = base + threadIdx.x;
-    long long nv = 0, nq = 0;
-    if (b < B) {
-      nv = totals[4 * b];
-      nq = (long long)totals[4 * b + 1] + totals[4 * b + 2] + totals[4 * b + 3];
-    }
-    long long tv, tq;
-    const long long ev = cm_block_exscan(nv, s_w, &tv);
-    const long long eq = cm_block_exscan(nq, s_w, &tq);
-    if (b < B) {
-      bases[2 * b] = carry_v + ev;
-      bases[2 * b + 1] = carry_q + eq;
-    }
-    carry_v += tv;
-    carry_q += tq;
   }
 }
 
@@ -319,7 +221,7 @@ int cm_classify(hipStream_t st, long long B, int X, int Y, int Z, const T* in, l
   if (!cm_layout(B, X, Y, Z, &lay) || workspace == nullptr) return (int)hipErrorInvalidValue;
   if (in == nullptr && (long long)X * Y * Z != 0) return (int)hipErrorInvalidValue;
   char* ws = (char*)workspace;
-  KAMD_LAUNCH_TIMED(kamd::K_CUBIC_CLASSIFY, (cm_classify_kernel<T>), dim3(cm_grid(lay.blocks)), dim3(CM_THREADS), 0, st, in, sn, sx,
+  KAMD_LAUNCH_TIMED(kamd::K_CUBIC_CLASSIFY, (cm_classify_kernel<T>), dim3(count_grid(lay.blocks)), dim3(CM_THREADS), 0, st, in, sn, sx,
                     sy, sz, X, Y, Z, (unsigned)lay.L, lay.G, lay.blocks, (unsigned char*)(ws + lay.codes),
                     (unsigned*)(ws + lay.counts));
   KAMD_RETURN_LAST_ERROR();
@@ -341,7 +243,7 @@ int kamd_cubic_meshes_classify_u8(void* stream, int64_t B, int X, int Y, int Z, 
 }
 int kamd_cubic_meshes_classify_f16(void* stream, int64_t B, int X, int Y, int Z, const void* voxelgrids, int64_t stride_n,
                                    int64_t stride_x, int64_t stride_y, int64_t stride_z, void* workspace) {
-  return cm_classify<cm_half>((hipStream_t)stream, (long long)B, X, Y, Z, (const cm_half*)voxelgrids, (long long)stride_n,
+  return cm_classify<half_bits>((hipStream_t)stream, (long long)B, X, Y, Z, (const half_bits*)voxelgrids, (long long)stride_n,
                               (long long)stride_x, (long long)stride_y, (long long)stride_z, workspace);
 }
 int kamd_cubic_meshes_classify_f32(void* stream, int64_t B, int X, int Y, int Z, const float* voxelgrids, int64_t stride_n,
@@ -358,10 +260,9 @@ int kamd_cubic_meshes_scan(void* stream, int64_t B, int X, int Y, int Z, void* w
   unsigned* totals = (unsigned*)(ws + lay.totals);
   {
     kamd::ProfScope prof(kamd::K_CUBIC_SCAN, st);
-    hipLaunchKernelGGL(cm_scan_kernel, dim3((unsigned)(B * 4)), dim3(CM_SCAN_THREADS), 0, st, lay.G, (unsigned*)(ws + lay.counts),
-                       totals);
-    hipLaunchKernelGGL(cm_bases_kernel, dim3(1), dim3(CM_THREADS), 0, st, (long long)B, (const unsigned*)totals,
-                       (long long*)(ws + lay.bases));
+    // a row = one counter of one item; its total is at most the L < 2^31 lattice points
+    rows_scan(st, (long long)B * 4, lay.G, (unsigned*)(ws + lay.counts), totals);
+    batch_bases<4>(st, (long long)B, (const unsigned*)totals, (long long*)(ws + lay.bases));
   }
   KAMD_CHECK(hipGetLastError());
   // the one host read of the call: the B x 4 totals size the outputs
@@ -374,7 +275,7 @@ int kamd_cubic_meshes_emit_vertices(void* stream, int64_t B, int X, int Y, int Z
   CmLayout lay;
   if (!cm_layout((long long)B, X, Y, Z, &lay) || workspace == nullptr || verts == nullptr) return (int)hipErrorInvalidValue;
   char* ws = (char*)workspace;
-  KAMD_LAUNCH_TIMED(kamd::K_CUBIC_VERTICES, cm_vertices_kernel, dim3(cm_grid(lay.blocks)), dim3(CM_THREADS), 0, (hipStream_t)stream, Y,
+  KAMD_LAUNCH_TIMED(kamd::K_CUBIC_VERTICES, cm_vertices_kernel, dim3(count_grid(lay.blocks)), dim3(CM_THREADS), 0, (hipStream_t)stream, Y,
                     Z, (unsigned)lay.L, lay.G, lay.blocks, (const unsigned char*)(ws + lay.codes),
                     (const unsigned*)(ws + lay.counts), (const long long*)(ws + lay.bases), (int*)(ws + lay.ranks), verts);
   KAMD_RETURN_LAST_ERROR();
@@ -387,12 +288,12 @@ int kamd_cubic_meshes_emit_faces(void* stream, int64_t B, int X, int Y, int Z, c
   const char* ws = (const char*)workspace;
   hipStream_t st = (hipStream_t)stream;
   if (is_trimesh)
-    KAMD_LAUNCH_TIMED(kamd::K_CUBIC_FACES, (cm_faces_kernel<true>), dim3(cm_grid(lay.blocks)), dim3(CM_THREADS), 0, st, Y, Z,
+    KAMD_LAUNCH_TIMED(kamd::K_CUBIC_FACES, (cm_faces_kernel<true>), dim3(count_grid(lay.blocks)), dim3(CM_THREADS), 0, st, Y, Z,
                       (unsigned)lay.L, lay.G, lay.blocks, (const unsigned char*)(ws + lay.codes),
                       (const unsigned*)(ws + lay.counts), (const unsigned*)(ws + lay.totals),
                       (const long long*)(ws + lay.bases), (const int*)(ws + lay.ranks), (long long*)faces);
   else
-    KAMD_LAUNCH_TIMED(kamd::K_CUBIC_FACES, (cm_faces_kernel<false>), dim3(cm_grid(lay.blocks)), dim3(CM_THREADS), 0, st, Y, Z,
+    KAMD_LAUNCH_TIMED(kamd::K_CUBIC_FACES, (cm_faces_kernel<false>), dim3(count_grid(lay.blocks)), dim3(CM_THREADS), 0, st, Y, Z,
                       (unsigned)lay.L, lay.G, lay.blocks, (const unsigned char*)(ws + lay.codes),
                       (const unsigned*)(ws + lay.counts), (const unsigned*)(ws + lay.totals),
                       (const long long*)(ws + lay.bases), (const int*)(ws + lay.ranks), (long long*)faces);

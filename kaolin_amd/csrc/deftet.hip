@@ -17,6 +17,7 @@
 //      pixel streaming the faces in order with ballot-prefix appends.
 // Arithmetic follows the reference expression by expression (-ffp-contract=off): integer outputs are bit-exact vs
 // oracle/deftet_oracle.inc, floats equal; results do not depend on the order in which hits arrive.
+#include "block_scan.h"
 #include "common.h"
 #include "profile.h"
 #include "tile_bins.h"
@@ -196,25 +197,11 @@ __global__ __launch_bounds__(DT_THREADS) void dt_count_kernel(int P, const T* __
 
 // ---- 3. exclusive scan of the NC counts in two launches: sums of 1024-entry blocks, then every block adds the sums
 //         before it and scans itself (entry NC receives the total); cursors start at the cell starts -----------------
-__device__ __forceinline__ int dt_block_inclusive(int v, int* s_wave) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int woff = 0;
-  for (int k = 0; k < wave; ++k) woff += s_wave[k];
-  return woff + inc;
-}
 __global__ __launch_bounds__(1024) void dt_scan_sums_kernel(DtWs w, int* __restrict__ sums) {
   __shared__ int s_wave[16];
   const int* start = w.start + (size_t)blockIdx.y * (w.nc + 4);
   const int i = blockIdx.x * 1024 + threadIdx.x;
-  const int tot = dt_block_inclusive(i < w.nc ? start[i] : 0, s_wave);
+  const int tot = block_inclusive(i < w.nc ? start[i] : 0, s_wave);
   if (threadIdx.x == 1023) sums[blockIdx.y * gridDim.x + blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(1024) void dt_scan_apply_kernel(DtWs w, const int* __restrict__ sums) {
@@ -225,14 +212,14 @@ __global__ __launch_bounds__(1024) void dt_scan_apply_kernel(DtWs w, const int* 
   const int* my = sums + blockIdx.y * gridDim.x;
   int part = 0;
   for (int k = threadIdx.x; k < (int)blockIdx.x; k += 1024) part += my[k];
-  const int before = dt_block_inclusive(part, s_wave);
+  const int before = block_inclusive(part, s_wave);
   if (threadIdx.x == 1023) s_off = before;
   __syncthreads();
   const int off = s_off;
   __syncthreads();
   const int i = blockIdx.x * 1024 + threadIdx.x;
   const int v = i < w.nc ? start[i] : 0;
-  const int inc = dt_block_inclusive(v, s_wave);
+  const int inc = block_inclusive(v, s_wave);
   if (i < w.nc) {
     start[i] = off + inc - v;
     cursor[i] = off + inc - v;

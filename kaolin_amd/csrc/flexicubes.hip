@@ -11,8 +11,8 @@
 //   1. fc_classify_kernel   one thread per cube: 8 sdf values -> case byte; a marked case recomputes the case of the cube across
 //                           its ambiguous face and inverts (255 - case) when that one is marked too.  Per workgroup and count
 //                           class the number of cubes and of incidences, from __ballot / __popcll.  No atomics.
-//      fc_scan_kernel       one workgroup per counter: exclusive scan in place, the total beside it.  HOST READ 1: the 8 totals
-//                           and the index-error flag.
+//      rows_scan_kernel     (count_scan.h) one workgroup per counter: exclusive scan in place, the total beside it.  HOST READ 1:
+//                           the 8 totals and the index-error flag.
 //   2. fc_compact_kernel    surface cube s (rank over all classes) -> (cube, case, first dual vertex, first incidence), and its
 //                           12 pairs key = first id << 32 | second id, value = 12 s + edge.
 //      ss_sort              the stable pair sort of sort_scan.h over 2 ceil(log2 V) bits: runs of equal edges, cubes ascending.
@@ -36,6 +36,7 @@
 // of an edge with the case's group count.  Not capturable in a graph: two host reads size the outputs.
 #include "common.h"
 #include "../../include/kaolin_amd.h"
+#include "count_scan.h"
 #include "sort_scan.h"
 
 #define KAMD_FLEXICUBES_QUALIFIER __device__ const
@@ -48,8 +49,6 @@ constexpr int FC_WAVES = FC_THREADS / 64;
 constexpr int FC_COUNTERS = 8;  // per count class k = 1..4: cubes (k - 1), incidences (4 + k - 1)
 constexpr int FC_TOTALS = 16;   // the 8 totals, the index-error flag at FC_FLAG
 constexpr int FC_FLAG = 8;
-constexpr int FC_SCAN_THREADS = 1024;
-constexpr int FC_SCAN_ITEMS = 8;
 
 // the corners of cube edge e, 3 bits each at bits [3 e, 3 e + 3): the first ends and the second ends
 constexpr unsigned long long fc_corners(int c0, int c1, int c2, int c3, int c4, int c5, int c6, int c7, int c8, int c9, int c10, int c11) {
@@ -97,29 +96,13 @@ __device__ __forceinline__ unsigned fc_case(const FcGrid& gr, long long c, unsig
   return code;
 }
 
-// a count of NB bits per thread: its sum over the lower lanes of the wavefront; the wavefront's sum to *s_wave
-template <int NB>
-__device__ __forceinline__ unsigned fc_wave_prefix(unsigned count, unsigned* s_wave) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  unsigned prefix = 0u, sum = 0u;
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const unsigned long long m = __ballot((count >> b) & 1u);
-    prefix += (unsigned)__popcll(m & below) << b;
-    sum += (unsigned)__popcll(m) << b;
-  }
-  if (lane == 0) *s_wave = sum;
-  return prefix;
-}
-
 // the 8 prefixes of a thread within its workgroup (class k at [k - 1] and [4 + k - 1]); s_waves: wavefront sums
 __device__ __forceinline__ void fc_block_prefixes(unsigned groups, unsigned incidences, unsigned (*s_waves)[FC_WAVES], unsigned* prefix) {
   const int wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 1; k <= 4; ++k) {
-    prefix[k - 1] = fc_wave_prefix<1>(groups == (unsigned)k ? 1u : 0u, &s_waves[k - 1][wave]);
-    prefix[4 + k - 1] = fc_wave_prefix<4>(groups == (unsigned)k ? incidences : 0u, &s_waves[4 + k - 1][wave]);
+    prefix[k - 1] = ballot_prefix<1>(groups == (unsigned)k ? 1u : 0u, &s_waves[k - 1][wave]);
+    prefix[4 + k - 1] = ballot_prefix<4>(groups == (unsigned)k ? incidences : 0u, &s_waves[4 + k - 1][wave]);
   }
 }
 
@@ -161,60 +144,6 @@ __global__ __launch_bounds__(FC_THREADS) void fc_classify_kernel(FcGrid gr, int 
     }
     __syncthreads();  // (s_waves is rewritten by the next round)
   }
-}
-
-// exclusive scan of one value per thread over the workgroup; *total = the sum.  s_w: (threads / 64 + 1) words.
-__device__ __forceinline__ unsigned fc_block_exscan(unsigned v, unsigned* s_w, unsigned* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  unsigned incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    const unsigned w = lane < nw ? s_w[lane] : 0u;
-    unsigned wi = w;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned o = __shfl_up(wi, d);
-      if (lane >= d) wi += o;
-    }
-    if (lane < nw) s_w[lane] = wi - w;
-    if (lane == nw - 1) s_w[nw] = wi;
-  }
-  __syncthreads();
-  const unsigned res = s_w[wave] + incl - v;
-  *total = s_w[nw];
-  __syncthreads();  // (s_w is rewritten by the next round)
-  return res;
-}
-
-// row = one counter: counts[row * G .. + G) <- its exclusive scan, totals[row] <- its sum (<= 12 C < 2^31)
-__global__ __launch_bounds__(FC_SCAN_THREADS) void fc_scan_kernel(long long G, unsigned* __restrict__ counts, unsigned* __restrict__ totals) {
-  __shared__ unsigned s_w[FC_SCAN_THREADS / 64 + 1];
-  unsigned* row = counts + (long long)blockIdx.x * G;
-  unsigned carry = 0u;
-  for (long long base = 0; base < G; base += FC_SCAN_THREADS * FC_SCAN_ITEMS) {
-    const long long first = base + (long long)threadIdx.x * FC_SCAN_ITEMS;
-    unsigned c[FC_SCAN_ITEMS], sum = 0u;
-#pragma unroll
-    for (int e = 0; e < FC_SCAN_ITEMS; ++e) {
-      c[e] = first + e < G ? row[first + e] : 0u;
-      sum += c[e];
-    }
-    unsigned total;
-    unsigned run = carry + fc_block_exscan(sum, s_w, &total);
-#pragma unroll
-    for (int e = 0; e < FC_SCAN_ITEMS; ++e) {
-      if (first + e < G) row[first + e] = run;
-      run += c[e];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
 // surf[s] = (cube, case, first dual vertex, first incidence); keys / vals [12 s + e]
@@ -608,7 +537,6 @@ __global__ __launch_bounds__(FC_THREADS) void fc_backward_kernel(FcGrid gr, cons
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-inline size_t fc_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 // the first workspace: [totals 16 u32][counts 8 x G u32][codes C u8]
 struct FcLayout {
   long long G;
@@ -618,9 +546,9 @@ bool fc_layout(long long C, FcLayout* lay) {
   if (C <= 0 || C > ((1ll << 31) - 1) / 12) return false;  // 12 C incidences and pairs at most: 32-bit ranks
   lay->G = (C + FC_THREADS - 1) / FC_THREADS;
   size_t o = 0;
-  lay->totals = o, o += fc_align16(FC_TOTALS * 4);
-  lay->counts = o, o += fc_align16((size_t)FC_COUNTERS * (size_t)lay->G * 4);
-  lay->codes = o, o += fc_align16((size_t)C);
+  lay->totals = o, o += kamd_align16(FC_TOTALS * 4);
+  lay->counts = o, o += kamd_align16((size_t)FC_COUNTERS * (size_t)lay->G * 4);
+  lay->codes = o, o += kamd_align16((size_t)C);
   lay->bytes = o;
   return true;
 }
@@ -634,25 +562,21 @@ bool fc_edge_layout(long long S, FcEdgeLayout* lay) {
   const long long n = S * 12;
   lay->n = n;
   size_t o = 0;
-  lay->keys = o, o += fc_align16((size_t)n * 8);
-  lay->keys_tmp = o, o += fc_align16((size_t)n * 8);
-  lay->vals = o, o += fc_align16((size_t)n * 8);
-  lay->vals_tmp = o, o += fc_align16((size_t)n * 8);
-  lay->is_quad = o, o += fc_align16((size_t)n * 4);
-  lay->is_flipped = o, o += fc_align16((size_t)n * 4);
-  lay->pos_quad = o, o += fc_align16((size_t)(n + 1) * 8);
-  lay->pos_flipped = o, o += fc_align16((size_t)(n + 1) * 8);
-  lay->hist = o, o += fc_align16(ss_sort_hist_entries(n) * 4);
-  lay->offs = o, o += fc_align16(ss_sort_offs_entries(n) * 8);
-  lay->sums = o, o += fc_align16(ss_sort_unique_sums_entries(n) * 8);
+  lay->keys = o, o += kamd_align16((size_t)n * 8);
+  lay->keys_tmp = o, o += kamd_align16((size_t)n * 8);
+  lay->vals = o, o += kamd_align16((size_t)n * 8);
+  lay->vals_tmp = o, o += kamd_align16((size_t)n * 8);
+  lay->is_quad = o, o += kamd_align16((size_t)n * 4);
+  lay->is_flipped = o, o += kamd_align16((size_t)n * 4);
+  lay->pos_quad = o, o += kamd_align16((size_t)(n + 1) * 8);
+  lay->pos_flipped = o, o += kamd_align16((size_t)(n + 1) * 8);
+  lay->hist = o, o += kamd_align16(ss_sort_hist_entries(n) * 4);
+  lay->offs = o, o += kamd_align16(ss_sort_offs_entries(n) * 8);
+  lay->sums = o, o += kamd_align16(ss_sort_unique_sums_entries(n) * 8);
   lay->bytes = o;
   return true;
 }
 
-unsigned fc_grid(long long blocks) {
-  const long long cap = (long long)KAMD_NUM_CU * 32;
-  return (unsigned)(blocks < 1 ? 1 : blocks < cap ? blocks : cap);
-}
 bool fc_make_grid(int64_t V, int64_t C, const float* sdf, const int64_t* cube_idx, int64_t st_cube, int64_t st_corner, FcGrid* gr) {
   if (V <= 0 || V >= (1ll << 31) || C <= 0 || sdf == nullptr || cube_idx == nullptr) return false;
   *gr = FcGrid{sdf, (const long long*)cube_idx, (long long)st_cube, (long long)st_corner, (long long)V, (long long)C};
@@ -684,9 +608,10 @@ int kamd_flexicubes_classify(void* stream, int64_t V, int64_t C, int rx, int ry,
   char* ws = (char*)workspace;
   unsigned* totals = (unsigned*)(ws + lay.totals);
   KAMD_CHECK(hipMemsetAsync(totals, 0, FC_TOTALS * 4, st));
-  hipLaunchKernelGGL(fc_classify_kernel, dim3(fc_grid(lay.G)), dim3(FC_THREADS), 0, st, gr, rx, ry, rz, lay.G,
+  hipLaunchKernelGGL(fc_classify_kernel, dim3(count_grid(lay.G)), dim3(FC_THREADS), 0, st, gr, rx, ry, rz, lay.G,
                      (unsigned char*)(ws + lay.codes), (unsigned*)(ws + lay.counts), totals);
-  hipLaunchKernelGGL(fc_scan_kernel, dim3(FC_COUNTERS), dim3(FC_SCAN_THREADS), 0, st, lay.G, (unsigned*)(ws + lay.counts), totals);
+  // a row = one counter; its total is at most the 12 C incidences: <= 12 C < 2^31
+  rows_scan(st, FC_COUNTERS, lay.G, (unsigned*)(ws + lay.counts), totals);
   KAMD_CHECK(hipGetLastError());
   // host read 1: the sizes of the surface and the index-error flag
   KAMD_CHECK(hipMemcpyAsync(host_totals, totals, (FC_FLAG + 1) * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -717,7 +642,7 @@ int kamd_flexicubes_edges(void* stream, int64_t V, int64_t C, int64_t S, const f
   KAMD_CHECK(hipMemsetAsync(ew + el.keys, 0, (size_t)el.n * 8, st));
   KAMD_CHECK(hipMemsetAsync(ew + el.vals, 0, (size_t)el.n * 8, st));
   KAMD_CHECK(hipMemsetAsync(surf, 0xFF, (size_t)S * 16, st));
-  hipLaunchKernelGGL(fc_compact_kernel, dim3(fc_grid(lay.G)), dim3(FC_THREADS), 0, st, gr, lay.G, (long long)S,
+  hipLaunchKernelGGL(fc_compact_kernel, dim3(count_grid(lay.G)), dim3(FC_THREADS), 0, st, gr, lay.G, (long long)S,
                      (const unsigned char*)(ws + lay.codes), (const unsigned*)(ws + lay.counts), (const unsigned*)(ws + lay.totals),
                      (int4*)surf, keys, vals);
   KAMD_CHECK(hipGetLastError());

@@ -1,6 +1,6 @@
 // Pieces of the uniform-grid pipeline shared by the exact nearest-point (sided_distance_grid.hip) and
 // nearest-triangle (triangle_distance.hip) searches: bounding box of a packed xyz array in partials, the grid geometry
-// every consumer re-derives from them, the cell index of a coordinate, and a workgroup scan.
+// every consumer re-derives from them, and the cell index of a coordinate.
 #pragma once
 #include "common.h"
 
@@ -74,22 +74,6 @@ __device__ __forceinline__ int sdg_axis_cell(float v, float lo, float inv, int G
   const float t = (v - lo) * inv;
   int c = (t >= 0.f) ? (t < (float)G ? (int)t : G - 1) : 0;  // NaN -> 0, +-inf -> clamped
   return c;
-}
-
-// ---- inclusive scan over a 1024-thread workgroup (the last thread's result is the total) ----------------------------
-__device__ __forceinline__ int sdg_block_inclusive(int v, int* s_wave) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < wave; ++w) woff += s_wave[w];
-  return woff + inc;
 }
 }  // namespace
 }  // namespace kamd

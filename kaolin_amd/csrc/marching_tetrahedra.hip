@@ -50,7 +50,6 @@ __constant__ unsigned char mt_tri[16][6] = {
     {1, 4, 0, 1, 5, 4}, {4, 2, 5, 0, 0, 0}, {4, 5, 2, 0, 0, 0}, {4, 1, 0, 4, 5, 1}, {3, 2, 0, 3, 5, 2}, {1, 3, 5, 0, 0, 0},
     {4, 1, 2, 4, 3, 1}, {3, 0, 4, 0, 0, 0}, {2, 0, 1, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
 
-inline size_t mt_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // ---- the (T, V) workspace: what classify leaves for the later stages -----------------------------------------------------
 struct MtLayout {
@@ -62,11 +61,11 @@ MtLayout mt_layout(long long T, long long V) {
   l.nchunk = ss_cdiv(T, MT_CHUNK);
   l.words = ss_cdiv(V, 64);
   size_t o = 0;
-  l.bitmap = o, o += mt_align((size_t)l.words * 8);
-  l.cases = o, o += mt_align((size_t)T);
-  l.counts = o, o += mt_align((size_t)l.nchunk * 2 * 4);
-  l.offs = o, o += mt_align(((size_t)l.nchunk * 2 + 1) * 8);
-  l.sums = o, o += mt_align(ss_scan_sums_entries(l.nchunk * 2) * 8);
+  l.bitmap = o, o += kamd_align16((size_t)l.words * 8);
+  l.cases = o, o += kamd_align16((size_t)T);
+  l.counts = o, o += kamd_align16((size_t)l.nchunk * 2 * 4);
+  l.offs = o, o += kamd_align16(((size_t)l.nchunk * 2 + 1) * 8);
+  l.sums = o, o += kamd_align16(ss_scan_sums_entries(l.nchunk * 2) * 8);
   l.bytes = o;
   return l;
 }
@@ -79,15 +78,15 @@ MtEdgeLayout mt_edge_layout(long long n_one, long long n_two) {
   MtEdgeLayout l;
   l.n = 3 * n_one + 4 * n_two;
   size_t o = 0;
-  l.entries = o, o += mt_align((size_t)(n_one + n_two) * 8);
-  l.keys_a = o, o += mt_align((size_t)l.n * 8);
-  l.keys_b = o, o += mt_align((size_t)l.n * 8);
-  l.uniq = o, o += mt_align((size_t)l.n * 8);
-  l.flags = o, o += mt_align((size_t)l.n * 4);
-  l.pos = o, o += mt_align(((size_t)l.n + 1) * 8);
-  l.hist = o, o += mt_align(ss_sort_hist_entries(l.n) * 4);
-  l.hoffs = o, o += mt_align(ss_sort_offs_entries(l.n) * 8);
-  l.sums = o, o += mt_align(ss_sort_unique_sums_entries(l.n) * 8);
+  l.entries = o, o += kamd_align16((size_t)(n_one + n_two) * 8);
+  l.keys_a = o, o += kamd_align16((size_t)l.n * 8);
+  l.keys_b = o, o += kamd_align16((size_t)l.n * 8);
+  l.uniq = o, o += kamd_align16((size_t)l.n * 8);
+  l.flags = o, o += kamd_align16((size_t)l.n * 4);
+  l.pos = o, o += kamd_align16(((size_t)l.n + 1) * 8);
+  l.hist = o, o += kamd_align16(ss_sort_hist_entries(l.n) * 4);
+  l.hoffs = o, o += kamd_align16(ss_sort_offs_entries(l.n) * 8);
+  l.sums = o, o += kamd_align16(ss_sort_unique_sums_entries(l.n) * 8);
   l.bytes = o;
   return l;
 }

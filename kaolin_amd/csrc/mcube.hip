@@ -18,9 +18,9 @@
 //   1. mc_classify_kernel   one thread per cell (dim2 fastest), the 8 values through the input's strides.  Writes the case byte and
 //                           two counts per workgroup (own vertices, triangles) from __ballot / __popcll and an LDS sum.  A
 //                           workgroup never straddles two items.  No atomics.
-//   2. mc_scan_kernel       one workgroup per (item, counter): exclusive scan of the workgroup counts in place, the total beside
-//                           it.  mc_bases_kernel: the int64 prefix over the items.  The host reads the B x 2 totals (ONE
-//                           synchronising copy for the whole batch) and allocates the outputs.
+//   2. rows_scan_kernel     (count_scan.h) one workgroup per (item, counter): exclusive scan of the workgroup counts in place,
+//                           the total beside it.  bases_kernel<2>: the int64 prefix over the items.  The host reads the B x 2
+//                           totals (ONE synchronising copy for the whole batch) and allocates the outputs.
 //   3. mc_vertices_kernel   first rank = workgroup offset + ballot prefix; writes the cell's float3s and its first rank into an
 //                           int32 array over the lattice (only where the cell owns a vertex: nothing else is ever gathered).
 //   4. mc_faces_kernel      walks the cell's table row (the 4 KB table sits in LDS: lanes index it divergently).  An edge id maps
@@ -33,6 +33,7 @@
 // at an index computed from prefix counts: bit-identical run to run, on any stream.  Indices derived from data (vertex rows, face
 // rows, the owner cell) are compared with their buffer's size before use.
 #include "common.h"
+#include "count_scan.h"
 #include "../../include/kaolin_amd.h"
 
 #define KAMD_MCUBE_QUALIFIER __device__ const
@@ -42,17 +43,6 @@ namespace {
 
 constexpr int MC_THREADS = 256;
 constexpr int MC_WAVES = MC_THREADS / 64;
-constexpr int MC_SCAN_THREADS = 1024;
-constexpr int MC_SCAN_ITEMS = 8;  // consecutive counts per thread and round of the scan: 8192 workgroups per round
-
-struct mc_half {
-  unsigned short bits;
-};
-__device__ __forceinline__ float mc_value(unsigned char v) { return (float)v; }
-__device__ __forceinline__ float mc_value(float v) { return v; }
-__device__ __forceinline__ float mc_value(mc_half v) { return __half2float(__ushort_as_half(v.bits)); }
-__device__ __forceinline__ void mc_store(float* p, float v) { *p = v; }
-__device__ __forceinline__ void mc_store(mc_half* p, float v) { p->bits = __half_as_ushort(__float2half(v)); }
 
 // per cell edge: the corner at its lower end as (dim0, dim1, dim2) offsets from the cell and the edge's axis, 5 bits each:
 // offset0 << 4 | offset1 << 3 | offset2 << 2 | axis, edge e at bits [5 e, 5 e + 5).  Edges (0,1) (1,2) (2,3) (3,0) (4,5) (5,6)
@@ -88,7 +78,7 @@ __device__ __forceinline__ float mc_fetch(const McGrid<T>& gr, const T* src, int
   } else {
     x = q0 < gr.X ? q0 : gr.X - 1, y = q1 < gr.Y ? q1 : gr.Y - 1, z = q2 < gr.Z ? q2 : gr.Z - 1;
   }
-  return mc_value(src[x * gr.sx + y * gr.sy + z * gr.sz]);
+  return grid_value(src[x * gr.sx + y * gr.sy + z * gr.sz]);
 }
 
 // the workspace: [totals B x 2 u32][bases B x 2 i64][counts B x 2 x G u32][ranks B x L i32][codes B x L u8], 16-byte aligned parts
@@ -97,7 +87,6 @@ struct McLayout {
   long long L, G, blocks;  // cells and workgroups per item; workgroups of the batch
   size_t totals, bases, counts, ranks, codes, bytes;
 };
-inline size_t mc_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 // false: nothing to do (an empty batch or grid) or a lattice whose 3 L possible vertices the 32-bit indices do not cover
 bool mc_layout(long long B, int X, int Y, int Z, int border, McLayout* lay) {
   if (B <= 0 || X < 1 || Y < 1 || Z < 1) return false;
@@ -110,34 +99,13 @@ bool mc_layout(long long B, int X, int Y, int Z, int border, McLayout* lay) {
   if (B > ((1ll << 31) - 1) / (lay->G > 2 ? lay->G : 2)) return false;  // (the grids: B G and B x 2 workgroups)
   lay->blocks = B * lay->G;
   size_t o = 0;
-  lay->totals = o, o += mc_align16((size_t)B * 2 * 4);
-  lay->bases = o, o += mc_align16((size_t)B * 2 * 8);
-  lay->counts = o, o += mc_align16((size_t)B * 2 * (size_t)lay->G * 4);
-  lay->ranks = o, o += mc_align16((size_t)B * (size_t)lay->L * 4);
-  lay->codes = o, o += mc_align16((size_t)B * (size_t)lay->L);
+  lay->totals = o, o += kamd_align16((size_t)B * 2 * 4);
+  lay->bases = o, o += kamd_align16((size_t)B * 2 * 8);
+  lay->counts = o, o += kamd_align16((size_t)B * 2 * (size_t)lay->G * 4);
+  lay->ranks = o, o += kamd_align16((size_t)B * (size_t)lay->L * 4);
+  lay->codes = o, o += kamd_align16((size_t)B * (size_t)lay->L);
   lay->bytes = o;
   return true;
-}
-
-unsigned mc_grid(long long blocks) {
-  const long long cap = (long long)KAMD_NUM_CU * 32;
-  return (unsigned)(blocks < cap ? blocks : cap);
-}
-
-// a count of NB bits per thread: its sum over the threads before this one of the wavefront, the wavefront's sum to s_wave[wave]
-template <int NB>
-__device__ __forceinline__ unsigned mc_wave_prefix(unsigned count, unsigned* s_wave) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  unsigned prefix = 0u, sum = 0u;
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const unsigned long long m = __ballot((count >> b) & 1u);
-    prefix += (unsigned)__popcll(m & below) << b;
-    sum += (unsigned)__popcll(m) << b;
-  }
-  if (lane == 0) s_wave[wave] = sum;
-  return prefix;
 }
 
 template <typename T>
@@ -168,8 +136,9 @@ __global__ __launch_bounds__(MC_THREADS) void mc_classify_kernel(McGrid<T> gr, f
       const bool real = gr.border || (i < gr.NX - 1 && j < gr.NY - 1 && k < gr.NZ - 1);
       nt = real ? s_ntri[code] : 0u;
     }
-    mc_wave_prefix<2>(nv, s_waves[0]);
-    mc_wave_prefix<3>(nt, s_waves[1]);
+    const int wave = threadIdx.x >> 6;
+    ballot_prefix<2>(nv, &s_waves[0][wave]);
+    ballot_prefix<3>(nt, &s_waves[1][wave]);
     __syncthreads();
     if (threadIdx.x < 2) {
       unsigned sum = 0u;
@@ -177,82 +146,6 @@ __global__ __launch_bounds__(MC_THREADS) void mc_classify_kernel(McGrid<T> gr, f
       counts[(item * 2 + threadIdx.x) * G + g] = sum;
     }
     __syncthreads();  // (s_waves is rewritten by the next round)
-  }
-}
-
-// exclusive scan of one value per thread over the workgroup; `total` = the sum.  s_w: (threads / 64 + 1) words.
-template <typename V>
-__device__ __forceinline__ V mc_block_exscan(V v, V* s_w, V* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  V incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const V o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    const V w = lane < nw ? s_w[lane] : (V)0;
-    V wi = w;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const V o = __shfl_up(wi, d);
-      if (lane >= d) wi += o;
-    }
-    if (lane < nw) s_w[lane] = wi - w;
-    if (lane == nw - 1) s_w[nw] = wi;
-  }
-  __syncthreads();
-  const V res = s_w[wave] + incl - v;
-  *total = s_w[nw];
-  __syncthreads();  // (s_w is rewritten by the next round)
-  return res;
-}
-
-// row = one counter of one item: counts[row * G .. + G) <- its exclusive scan, totals[row] <- its sum (<= 5 L < 2^32)
-__global__ __launch_bounds__(MC_SCAN_THREADS) void mc_scan_kernel(long long G, unsigned* __restrict__ counts,
-                                                                  unsigned* __restrict__ totals) {
-  __shared__ unsigned s_w[MC_SCAN_THREADS / 64 + 1];
-  unsigned* row = counts + (long long)blockIdx.x * G;
-  unsigned carry = 0u;
-  for (long long base = 0; base < G; base += MC_SCAN_THREADS * MC_SCAN_ITEMS) {
-    const long long first = base + (long long)threadIdx.x * MC_SCAN_ITEMS;
-    unsigned c[MC_SCAN_ITEMS], sum = 0u;
-#pragma unroll
-    for (int e = 0; e < MC_SCAN_ITEMS; ++e) {
-      c[e] = first + e < G ? row[first + e] : 0u;
-      sum += c[e];
-    }
-    unsigned total;
-    unsigned run = carry + mc_block_exscan(sum, s_w, &total);
-#pragma unroll
-    for (int e = 0; e < MC_SCAN_ITEMS; ++e) {
-      if (first + e < G) row[first + e] = run;
-      run += c[e];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
-
-// bases[2 b], bases[2 b + 1] <- the vertices and the triangles of the items before b (int64: the batch may exceed 2^31 rows)
-__global__ __launch_bounds__(MC_THREADS) void mc_bases_kernel(long long B, const unsigned* __restrict__ totals,
-                                                              long long* __restrict__ bases) {
-  __shared__ long long s_w[MC_WAVES + 1];
-  long long carry_v = 0, carry_t = 0;
-  for (long long base = 0; base < B; base += MC_THREADS) {
-    const long long b = base + threadIdx.x;
-    const long long nv = b < B ? (long long)totals[2 * b] : 0, nt = b < B ? (long long)totals[2 * b + 1] : 0;
-    long long tv, tt;
-    const long long ev = mc_block_exscan(nv, s_w, &tv);
-    const long long et = mc_block_exscan(nt, s_w, &tt);
-    if (b < B) {
-      bases[2 * b] = carry_v + ev;
-      bases[2 * b + 1] = carry_t + et;
-    }
-    carry_v += tv;
-    carry_t += tt;
   }
 }
 
@@ -269,7 +162,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_vertices_kernel(McGrid<T> gr, f
     const long long item = blk / G, g = blk - item * G;
     const unsigned p = (unsigned)g * MC_THREADS + threadIdx.x;
     const unsigned own = p < L ? mc_own(codes[item * L + p]) : 0u;
-    unsigned prefix = mc_wave_prefix<2>((unsigned)__popc(own), s_waves);
+    unsigned prefix = ballot_prefix<2>((unsigned)__popc(own), &s_waves[wave]);
     __syncthreads();
     for (int w = 0; w < wave; ++w) prefix += s_waves[w];
     if (own != 0u) {
@@ -338,7 +231,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_faces_kernel(int NX, int NY, in
       const bool real = border || (i < NX - 1 && j < NY - 1 && k < NZ - 1);
       nt = real ? s_ntri[code] : 0u;
     }
-    unsigned prefix = mc_wave_prefix<3>(nt, s_waves);
+    unsigned prefix = ballot_prefix<3>(nt, &s_waves[wave]);
     __syncthreads();
     for (int w = 0; w < wave; ++w) prefix += s_waves[w];
     if (nt != 0u) {
@@ -390,7 +283,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_backward_kernel(McGrid<T> gr, f
     const T* src = gr.in + item * gr.sn;
     const int q[3] = {x + 1, y + 1, z + 1};  // the voxel's lattice point
     const unsigned p = ((unsigned)q[0] * (unsigned)gr.NY + (unsigned)q[1]) * (unsigned)gr.NZ + (unsigned)q[2];
-    const float f = mc_value(src[x * gr.sx + y * gr.sy + z * gr.sz]);
+    const float f = grid_value(src[x * gr.sx + y * gr.sy + z * gr.sz]);
     const unsigned char* cd = codes + item * L;
     const int* rk = ranks + item * L;
     const long long base = bases[2 * item];
@@ -414,7 +307,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_backward_kernel(McGrid<T> gr, f
         const float term = grad_verts[row * 3 + a] * ((iso - other) / (d * d));
         acc += up ? term : -term;
       }
-    mc_store(grad + n, acc);
+    grid_store(grad + n, acc);
   }
 }
 
@@ -434,7 +327,7 @@ int mc_classify(hipStream_t st, long long B, int X, int Y, int Z, int border, co
   if (!mc_make_grid(B, X, Y, Z, border, in, sn, sx, sy, sz, &lay, &gr) || workspace == nullptr || !(iso == iso))
     return (int)hipErrorInvalidValue;
   char* ws = (char*)workspace;
-  hipLaunchKernelGGL((mc_classify_kernel<T>), dim3(mc_grid(lay.blocks)), dim3(MC_THREADS), 0, st, gr, iso, (unsigned)lay.L, lay.G,
+  hipLaunchKernelGGL((mc_classify_kernel<T>), dim3(count_grid(lay.blocks)), dim3(MC_THREADS), 0, st, gr, iso, (unsigned)lay.L, lay.G,
                      lay.blocks, (unsigned char*)(ws + lay.codes), (unsigned*)(ws + lay.counts));
   KAMD_RETURN_LAST_ERROR();
 }
@@ -447,7 +340,7 @@ int mc_emit_vertices(hipStream_t st, long long B, int X, int Y, int Z, int borde
   if (!mc_make_grid(B, X, Y, Z, border, in, sn, sx, sy, sz, &lay, &gr) || workspace == nullptr || verts == nullptr || verts_rows < 0)
     return (int)hipErrorInvalidValue;
   char* ws = (char*)workspace;
-  hipLaunchKernelGGL((mc_vertices_kernel<T>), dim3(mc_grid(lay.blocks)), dim3(MC_THREADS), 0, st, gr, iso, (unsigned)lay.L, lay.G,
+  hipLaunchKernelGGL((mc_vertices_kernel<T>), dim3(count_grid(lay.blocks)), dim3(MC_THREADS), 0, st, gr, iso, (unsigned)lay.L, lay.G,
                      lay.blocks, (const unsigned char*)(ws + lay.codes), (const unsigned*)(ws + lay.counts),
                      (const long long*)(ws + lay.bases), (int*)(ws + lay.ranks), verts, verts_rows);
   KAMD_RETURN_LAST_ERROR();
@@ -463,7 +356,7 @@ int mc_backward(hipStream_t st, long long B, int X, int Y, int Z, const T* in, l
     return (int)hipErrorInvalidValue;
   const char* ws = (const char*)workspace;
   const long long total = B * X * Y * Z;
-  hipLaunchKernelGGL((mc_backward_kernel<T>), dim3(mc_grid((total + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, gr, iso,
+  hipLaunchKernelGGL((mc_backward_kernel<T>), dim3(count_grid((total + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, gr, iso,
                      (unsigned)lay.L, total, (const unsigned char*)(ws + lay.codes), (const long long*)(ws + lay.bases),
                      (const int*)(ws + lay.ranks), grad_verts, verts_rows, grad);
   KAMD_RETURN_LAST_ERROR();
@@ -485,7 +378,7 @@ int kamd_mcube_classify_u8(void* stream, int64_t B, int X, int Y, int Z, int bor
 }
 int kamd_mcube_classify_f16(void* stream, int64_t B, int X, int Y, int Z, int border, const void* voxelgrids, int64_t stride_n,
                             int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace) {
-  return mc_classify<mc_half>((hipStream_t)stream, (long long)B, X, Y, Z, border, (const mc_half*)voxelgrids, (long long)stride_n,
+  return mc_classify<half_bits>((hipStream_t)stream, (long long)B, X, Y, Z, border, (const half_bits*)voxelgrids, (long long)stride_n,
                               (long long)stride_x, (long long)stride_y, (long long)stride_z, iso_value, workspace);
 }
 int kamd_mcube_classify_f32(void* stream, int64_t B, int X, int Y, int Z, int border, const float* voxelgrids, int64_t stride_n,
@@ -501,9 +394,9 @@ int kamd_mcube_scan(void* stream, int64_t B, int X, int Y, int Z, int border, vo
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   unsigned* totals = (unsigned*)(ws + lay.totals);
-  hipLaunchKernelGGL(mc_scan_kernel, dim3((unsigned)(B * 2)), dim3(MC_SCAN_THREADS), 0, st, lay.G, (unsigned*)(ws + lay.counts), totals);
-  hipLaunchKernelGGL(mc_bases_kernel, dim3(1), dim3(MC_THREADS), 0, st, (long long)B, (const unsigned*)totals,
-                     (long long*)(ws + lay.bases));
+  // a row = one counter of one item; its total is at most 5 triangles (or 3 vertices) per cell: <= 5 L < 2^32
+  rows_scan(st, (long long)B * 2, lay.G, (unsigned*)(ws + lay.counts), totals);
+  batch_bases<2>(st, (long long)B, (const unsigned*)totals, (long long*)(ws + lay.bases));
   KAMD_CHECK(hipGetLastError());
   // the one host read of the call: the B x 2 totals size the outputs
   KAMD_CHECK(hipMemcpyAsync(host_totals, totals, (size_t)B * 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -521,7 +414,7 @@ int kamd_mcube_emit_vertices_u8(void* stream, int64_t B, int X, int Y, int Z, in
 int kamd_mcube_emit_vertices_f16(void* stream, int64_t B, int X, int Y, int Z, int border, const void* voxelgrids, int64_t stride_n,
                                  int64_t stride_x, int64_t stride_y, int64_t stride_z, float iso_value, void* workspace, float* verts,
                                  int64_t verts_rows) {
-  return mc_emit_vertices<mc_half>((hipStream_t)stream, (long long)B, X, Y, Z, border, (const mc_half*)voxelgrids, (long long)stride_n,
+  return mc_emit_vertices<half_bits>((hipStream_t)stream, (long long)B, X, Y, Z, border, (const half_bits*)voxelgrids, (long long)stride_n,
                                    (long long)stride_x, (long long)stride_y, (long long)stride_z, iso_value, workspace, verts,
                                    (long long)verts_rows);
 }
@@ -539,7 +432,7 @@ int kamd_mcube_emit_faces(void* stream, int64_t B, int X, int Y, int Z, int bord
   if (!mc_layout((long long)B, X, Y, Z, border, &lay) || workspace == nullptr || faces == nullptr || faces_rows < 0)
     return (int)hipErrorInvalidValue;
   const char* ws = (const char*)workspace;
-  hipLaunchKernelGGL(mc_faces_kernel, dim3(mc_grid(lay.blocks)), dim3(MC_THREADS), 0, (hipStream_t)stream, lay.NX, lay.NY, lay.NZ,
+  hipLaunchKernelGGL(mc_faces_kernel, dim3(count_grid(lay.blocks)), dim3(MC_THREADS), 0, (hipStream_t)stream, lay.NX, lay.NY, lay.NZ,
                      border ? 1 : 0, (unsigned)lay.L, lay.G, lay.blocks, (const unsigned char*)(ws + lay.codes),
                      (const unsigned*)(ws + lay.counts), (const long long*)(ws + lay.bases), (const int*)(ws + lay.ranks),
                      (long long*)faces, (long long)faces_rows);
@@ -549,9 +442,9 @@ int kamd_mcube_emit_faces(void* stream, int64_t B, int X, int Y, int Z, int bord
 int kamd_mcube_backward_f16(void* stream, int64_t B, int X, int Y, int Z, const void* voxelgrids, int64_t stride_n, int64_t stride_x,
                             int64_t stride_y, int64_t stride_z, float iso_value, const void* workspace, const float* grad_verts,
                             int64_t verts_rows, void* grad_voxelgrids) {
-  return mc_backward<mc_half>((hipStream_t)stream, (long long)B, X, Y, Z, (const mc_half*)voxelgrids, (long long)stride_n,
+  return mc_backward<half_bits>((hipStream_t)stream, (long long)B, X, Y, Z, (const half_bits*)voxelgrids, (long long)stride_n,
                               (long long)stride_x, (long long)stride_y, (long long)stride_z, iso_value, workspace, grad_verts,
-                              (long long)verts_rows, (mc_half*)grad_voxelgrids);
+                              (long long)verts_rows, (half_bits*)grad_voxelgrids);
 }
 int kamd_mcube_backward_f32(void* stream, int64_t B, int X, int Y, int Z, const float* voxelgrids, int64_t stride_n, int64_t stride_x,
                             int64_t stride_y, int64_t stride_z, float iso_value, const void* workspace, const float* grad_verts,

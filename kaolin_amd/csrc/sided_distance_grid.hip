@@ -31,6 +31,7 @@
 // agree on every cell), the sorted copy keeps the doubles, every distance is the reference's double expression, and the
 // geometric bound's head-room (67 float ulps) covers the rounding of the coordinates it is computed from.  A query whose
 // coordinates do not fit a float walks all targets (exact, slow, rare).
+#include "block_scan.h"
 #include "common.h"
 #include "profile.h"
 #include "sided_distance_grid.h"
@@ -389,7 +390,7 @@ __global__ __launch_bounds__(SDG_BUILD_THREADS) void sdg_build(CloudT<T> X, Clou
     const int* cnt = (first ? X.count : Y.count) + (size_t)b * NC;
     const int i = base + tid;
     __syncthreads();
-    const int tot = sdg_block_inclusive(i < NC ? sdg_ld(cnt + i) : 0, s_wave);
+    const int tot = block_inclusive(i < NC ? sdg_ld(cnt + i) : 0, s_wave);
     if (tid == SDG_BUILD_THREADS - 1) sdg_st(sums + ((size_t)z * B + b) * scan_blocks + blk, tot);
   }
   KAMD_SDG_T(5)
@@ -409,11 +410,11 @@ __global__ __launch_bounds__(SDG_BUILD_THREADS) void sdg_build(CloudT<T> X, Clou
     const int i = base + tid;
     const int v = i < NC ? sdg_ld(cnt + i) : 0;
     __syncthreads();  // s_wave / s_off of the previous unit have been read
-    const int before = sdg_block_inclusive(part, s_wave);
+    const int before = block_inclusive(part, s_wave);
     if (tid == SDG_BUILD_THREADS - 1) s_off = before;
     __syncthreads();
     const int off = s_off;
-    const int inc = sdg_block_inclusive(v, s_wave);
+    const int inc = block_inclusive(v, s_wave);
     if (i < NC) sdg_st(start + i, off + inc - v);
     if (i == NC - 1) sdg_st(start + NC, off + inc);
   }

@@ -1,13 +1,14 @@
 // The scan / sort / unique primitives of every sort-based pipeline (marching tetrahedra, tet and Loop subdivision, the SPC octree
 // build, the dual octree, mesh / Gaussians / point clouds to SPC, bf_recon, SPC ray tracing):
-//   * a two-level block scan of 64-bit sums: an exclusive one of ints into n + 1 int64 offsets whose length may live on the
-//     device, and an inclusive one into ints of the ints themselves or of the bit counts of bytes;
+//   * a two-level scan of 64-bit sums over the workgroup scan of block_scan.h: an exclusive one of ints into n + 1 int64 offsets
+//     whose length may live on the device, and an inclusive one into ints of the ints themselves or of the bit counts of bytes;
 //   * a stable 8-bit LSD radix sort of 64-bit keys, alone or with a 64-bit value each, over a list of pass shifts;
 //   * the heads of the runs of equal (shifted) keys, their scan, the compaction of the heads, and the rank of a key among them.
 // The sizes of their scratch are sort_scan_host.h's.  Every name lives in an unnamed namespace: each translation unit gets its
 // own copy.  int64_t / long long and uint64_t / unsigned long long are distinct types of one width and the pipelines spell
 // their buffers either way: the host functions take any 8-byte integer (SS_IS_WORD) and the kernels see (unsigned) long long.
 #pragma once
+#include "block_scan.h"
 #include "common.h"
 #include "sort_scan_host.h"
 
@@ -17,21 +18,7 @@ namespace {
 
 inline unsigned ss_grid(long long items, int per_block) { return (unsigned)(items > 0 ? ss_cdiv(items, per_block) : 1); }
 
-// ---- the block scan: inclusive sums of one value per thread of a 1024-thread workgroup ------------------------------------------
-__device__ __forceinline__ long long ss_block_inclusive(long long v, long long* s_wave) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  long long woff = 0;
-  for (int k = 0; k < wave; ++k) woff += s_wave[k];
-  return woff + inc;
-}
+// ---- the scan: block_inclusive (block_scan.h) over the 1024 threads of a workgroup, 64-bit sums ----------------------------------
 // what an element adds to the sum: an int itself, a byte its bit count
 __device__ __forceinline__ long long ss_scan_value(const int* in, long long i) { return in[i]; }
 __device__ __forceinline__ long long ss_scan_value(const unsigned char* in, long long i) { return __popc((unsigned)in[i]); }
@@ -44,7 +31,7 @@ __global__ __launch_bounds__(SS_SCAN_BLOCK) void ss_scan_sums_kernel(long long n
   __shared__ long long s_wave[16];
   const long long n = n_ptr ? *n_ptr : n_host;
   const long long i = (long long)blockIdx.x * SS_SCAN_BLOCK + threadIdx.x;
-  const long long tot = ss_block_inclusive(i < n ? ss_scan_value(in, i) : 0, s_wave);
+  const long long tot = block_inclusive(i < n ? ss_scan_value(in, i) : 0, s_wave);
   if (threadIdx.x == SS_SCAN_BLOCK - 1) sums[blockIdx.x] = tot;
 }
 // the inclusive sum at element i = blockIdx.x * 1024 + threadIdx.x over all elements up to it; *own = the element's own value
@@ -55,14 +42,14 @@ __device__ __forceinline__ long long ss_scan_apply(long long n, const In* __rest
   __shared__ long long s_off;
   long long part = 0;
   for (int k = threadIdx.x; k < (int)blockIdx.x; k += SS_SCAN_BLOCK) part += sums[k];
-  const long long before = ss_block_inclusive(part, s_wave);
+  const long long before = block_inclusive(part, s_wave);
   if (threadIdx.x == SS_SCAN_BLOCK - 1) s_off = before;
   __syncthreads();
   const long long off = s_off;
   __syncthreads();
   const long long i = (long long)blockIdx.x * SS_SCAN_BLOCK + threadIdx.x;
   *own = i < n ? ss_scan_value(in, i) : 0;
-  return off + ss_block_inclusive(*own, s_wave);
+  return off + block_inclusive(*own, s_wave);
 }
 // exclusive, n + 1 outputs: out[n] = the total (n == 0: out[0] = 0)
 __global__ __launch_bounds__(SS_SCAN_BLOCK) void ss_scan_exclusive_kernel(long long n_host, const long long* __restrict__ n_ptr,

@@ -2,6 +2,7 @@
 // shifts, wave scans and the 64 x 64 bit transpose.  (The round-1 binning that lived here -- one bit per (32 x 32 tile,
 // face), cleared and scanned on every call -- was replaced by the tile face lists of tile_lists.h.)
 #pragma once
+#include "block_scan.h"
 #include "common.h"
 
 namespace kamd {
@@ -175,13 +176,5 @@ __device__ __forceinline__ int wave_inclusive_scan_dpp(int v) {
   return v + (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
 }
 // ---- inclusive scan over a wavefront ----------------------------------------------------------------
-__device__ __forceinline__ int wave_inclusive_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
+__device__ __forceinline__ int wave_inclusive_scan(int v) { return wave_inclusive(v, (int)(threadIdx.x & 63)); }
 }  // namespace kamd

@@ -31,6 +31,7 @@
 //     and only the tiles that come closer than a query's best bound are staged and walked (identical results).
 #include <string.h>
 #include <hip/hip_runtime.h>
+#include "block_scan.h"
 #include "common.h"
 #include <stdlib.h>
 #include "profile.h"

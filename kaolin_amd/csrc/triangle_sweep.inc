@@ -233,12 +233,7 @@ __global__ __launch_bounds__(256) void ts_scan_apply_kernel(int* __restrict__ fc
     v[k] = i < n ? cnt[i] : 0;
     sum += v[k];
   }
-  int inc = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
+  const int inc = wave_inclusive(sum, lane);
   if (lane == 63) s_w2[wave] = inc;
   __syncthreads();
   int off = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]) + inc - sum;

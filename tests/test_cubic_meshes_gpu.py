@@ -109,6 +109,9 @@ def test_cpu_path_equals_gpu_path_random(is_trimesh):
     g = torch.Generator().manual_seed(11)
     x = torch.rand((2, 33, 17, 65), generator=g) < 0.5
     assert_same_meshes(voxelgrids_to_cubic_meshes(x.to(DEV), is_trimesh), voxelgrids_to_cubic_meshes(x, is_trimesh), device=DEV)
+    # 258 small items: the prefix over the batch walks it in rounds of 256, so the last two items start after a carried round
+    many = torch.rand((258, 2, 3, 2), generator=g) < 0.5
+    assert_same_meshes(voxelgrids_to_cubic_meshes(many.to(DEV), is_trimesh), voxelgrids_to_cubic_meshes(many, is_trimesh), device=DEV)
 
 
 @pytest.fixture(scope='module')

@@ -54,6 +54,10 @@ def test_golden(n):
 def test_all_256_cases():
     x = all_cases_batch()
     assert_equals_oracle(x, got=gpu(x))
+    # 258 items: the prefix over the batch walks it in rounds of 256, so items 256 (empty) and 257 start after a carried round
+    more = torch.cat([x, x[:1], x[105:106]])
+    assert more.shape == (258, 2, 2, 2) and not more[256].any() and more[257].any()
+    assert_equals_oracle(more, got=gpu(more))
 
 
 @pytest.mark.parametrize('dtype', HIP_DTYPES + CAST_DTYPES, ids=lambda d: str(d).split('.')[-1])
