@@ -1502,6 +1502,71 @@ int kamd_vertex_gather_backward_f64(void* stream, int64_t B, int64_t F, int64_t 
                                     int64_t faces_stride_f, int64_t faces_stride_k, const int32_t* offsets, int mean, double* grad);
 
 /* ------------------------------------------------------------------------- */
+/* ops.mesh face_areas / sample_points (csrc/sample_points.hip; the reference  */
+/* is pure torch, kaolin/ops/mesh/trianglemesh.py:30-311: these entry points   */
+/* exist only on our side).  faces: int64 with element strides.  Items:        */
+/* items == NULL (batched): item b is the F faces, vertices b of (B, V, 3)     */
+/*   with element strides, areas / cdf row b of (B, F);                        */
+/* items = B rows (face_begin, face_end, vertex_base) of int64 on the device   */
+/*   (packed): item b is faces [face_begin, face_end) of the F packed faces,   */
+/*   ids counted from vertex_base in the V packed vertices (vs_b unused),      */
+/*   areas / cdf (F).  A face range is clipped to [0, F); a vertex id (+ base) */
+/*   outside [0, V) gives NaN and takes no gradient.                           */
+/* face_areas_*: one thread per face, sqrt((a + b) + c) 0.5 of the reference's */
+/*   expression, one rounding per operation.  face_areas_backward_*: the       */
+/*   per-corner gradient (B F | F, 3, 3) by plain stores (the reference's      */
+/*   autograd expression; NaN at a zero-area face), to be summed per vertex by */
+/*   kamd_vertex_gather_*.                                                     */
+/* sample_cdf_*: cdf = the inclusive float64 sums of every item's areas in a   */
+/*   fixed order: 1 launch when max_faces (the largest item) fits one tile of  */
+/*   the scan, else 3.  workspace: kamd_sample_cdf_workspace(B, max_faces)     */
+/*   bytes (host arithmetic; 0: out of range).                                 */
+/* sample_points_*: N samples per item from r (B, N) float64 and uv (B, N, 2), */
+/*   contiguous: t = min(r total, nextbelow(total)), the first face with       */
+/*   cdf > t (and area > 0), u = sqrt(uv0), w = (1 - u, u (1 - uv1), u uv1),   */
+/*   points (B, N, 3) = (w0 v0 + w1 v1) + w2 v2, face_choices (B, N) (packed:  */
+/*   merged ids), features (B, N, D) from face_features (B, F, 3, D) with      */
+/*   element strides (D = 0: none; batched only).  An item whose total is not  */
+/*   positive and finite: NaN, choice face_begin.  One launch, no atomics.     */
+/* sample_points_backward_*: one launch; w_k g added with float atomics to     */
+/*   grad_vertices (B, V, 3 | V, 3) and grad_face_features (B, F, 3, D), both  */
+/*   contiguous and zeroed by the caller, either may be NULL.                  */
+/* ------------------------------------------------------------------------- */
+int kamd_face_areas_f32(void* stream, int64_t B, int64_t F, int64_t V, const int64_t* items, const float* vertices, int64_t vs_b,
+                        int64_t vs_v, int64_t vs_c, const int64_t* faces, int64_t fs_f, int64_t fs_k, float* areas);
+int kamd_face_areas_f64(void* stream, int64_t B, int64_t F, int64_t V, const int64_t* items, const double* vertices, int64_t vs_b,
+                        int64_t vs_v, int64_t vs_c, const int64_t* faces, int64_t fs_f, int64_t fs_k, double* areas);
+int kamd_face_areas_backward_f32(void* stream, int64_t B, int64_t F, int64_t V, const int64_t* items, const float* vertices,
+                                 int64_t vs_b, int64_t vs_v, int64_t vs_c, const int64_t* faces, int64_t fs_f, int64_t fs_k,
+                                 const float* grad_areas, int64_t gs_b, int64_t gs_f, float* grad_corners);
+int kamd_face_areas_backward_f64(void* stream, int64_t B, int64_t F, int64_t V, const int64_t* items, const double* vertices,
+                                 int64_t vs_b, int64_t vs_v, int64_t vs_c, const int64_t* faces, int64_t fs_f, int64_t fs_k,
+                                 const double* grad_areas, int64_t gs_b, int64_t gs_f, double* grad_corners);
+size_t kamd_sample_cdf_workspace(int64_t B, int64_t F);
+int kamd_sample_cdf_f32(void* stream, int64_t B, int64_t F, int64_t max_faces, const int64_t* items, const float* areas, double* cdf,
+                        void* workspace, size_t workspace_bytes);
+int kamd_sample_cdf_f64(void* stream, int64_t B, int64_t F, int64_t max_faces, const int64_t* items, const double* areas, double* cdf,
+                        void* workspace, size_t workspace_bytes);
+int kamd_sample_points_f32(void* stream, int64_t B, int64_t F, int64_t V, int64_t N, int64_t D, const int64_t* items,
+                           const float* vertices, int64_t vs_b, int64_t vs_v, int64_t vs_c, const int64_t* faces, int64_t fs_f,
+                           int64_t fs_k, const void* areas, int areas_bytes, const double* cdf, const double* r, const float* uv,
+                           const float* face_features, int64_t ff_b, int64_t ff_f, int64_t ff_k, int64_t ff_d, float* points,
+                           int64_t* face_choices, float* features);
+int kamd_sample_points_f64(void* stream, int64_t B, int64_t F, int64_t V, int64_t N, int64_t D, const int64_t* items,
+                           const double* vertices, int64_t vs_b, int64_t vs_v, int64_t vs_c, const int64_t* faces, int64_t fs_f,
+                           int64_t fs_k, const void* areas, int areas_bytes, const double* cdf, const double* r, const double* uv,
+                           const double* face_features, int64_t ff_b, int64_t ff_f, int64_t ff_k, int64_t ff_d, double* points,
+                           int64_t* face_choices, double* features);
+int kamd_sample_points_backward_f32(void* stream, int64_t B, int64_t F, int64_t V, int64_t N, int64_t D, const int64_t* items,
+                                    const int64_t* faces, int64_t fs_f, int64_t fs_k, const double* cdf, const float* uv,
+                                    const int64_t* face_choices, const float* grad_points, const float* grad_features,
+                                    float* grad_vertices, float* grad_face_features);
+int kamd_sample_points_backward_f64(void* stream, int64_t B, int64_t F, int64_t V, int64_t N, int64_t D, const int64_t* items,
+                                    const int64_t* faces, int64_t fs_f, int64_t fs_k, const double* cdf, const double* uv,
+                                    const int64_t* face_choices, const double* grad_points, const double* grad_features,
+                                    double* grad_vertices, double* grad_face_features);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -2032,12 +2032,217 @@ def vertex_gather_backward_cuda(grad_out, faces, offsets, mean):
     return grad
 
 
+# ---- kaolin._C.ops.mesh: face areas and surface sampling on csrc/sample_points.hip (no reference counterpart: pure torch there) -------
+def _sp_mesh(fn, vertices, faces, items):
+    """Checks of the mesh arguments shared by the four operators -> (sfx, B, F, V, items, max_faces, vertex strides)"""
+    torch_check(isinstance(vertices, torch.Tensor) and vertices.is_cuda, f'{fn}: vertices must be a CUDA tensor')
+    sfx = _lib.dtype_suffix(vertices.dtype, fn)
+    torch_check(isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dim() == 2 and faces.size(1) == 3 and
+                faces.dtype == torch.long and faces.device == vertices.device,
+                f'{fn}: faces must be a long CUDA tensor of size (num_faces, 3) on the device of vertices')
+    F = faces.size(0)
+    torch_check(F >= 1, f'{fn}: no faces')
+    if items is None:
+        torch_check(vertices.dim() == 3 and vertices.size(2) == 3, f'{fn}: vertices must be of size (batch_size, num_vertices, 3)')
+        B, V = vertices.size(0), vertices.size(1)
+        strides, max_faces = vertices.stride(), F
+    else:
+        torch_check(vertices.dim() == 2 and vertices.size(1) == 3, f'{fn}: packed vertices must be of size (num_vertices, 3)')
+        torch_check(isinstance(items, tuple) and len(items) == 2 and isinstance(items[0], torch.Tensor) and
+                    items[0].dtype == torch.long and items[0].device == vertices.device and items[0].dim() == 2 and
+                    items[0].size(1) == 3 and items[0].is_contiguous(),
+                    f'{fn}: items must be (a contiguous long tensor of size (batch_size, 3) on the device of vertices, max_faces)')
+        items, max_faces = items[0], int(items[1])
+        B, V = items.size(0), vertices.size(0)
+        torch_check(1 <= max_faces <= F, f'{fn}: max_faces must be in [1, num_faces]')
+        strides = (0,) + tuple(vertices.stride())
+    torch_check(B >= 1 and V >= 1, f'{fn}: vertices of size {tuple(vertices.shape)}: every extent must be at least 1')
+    return sfx, B, F, V, items, max_faces, strides
+
+
+def _sp_per_face(fn, t, name, B, F, packed, dev):
+    want = (F,) if packed else (B, F)
+    torch_check(isinstance(t, torch.Tensor) and t.device == dev and tuple(t.shape) == want and
+                t.dtype in (torch.float32, torch.float64), f'{fn}: {name} must be a float / double tensor of size {want} on the device of vertices')
+
+
+def face_areas_forward_cuda(vertices, faces, items=None):
+    """vertices (B, V, 3) float / double of any strides, faces (F, 3) long of any strides -> areas (B, F); with ``items`` =
+    (the device table (B, 3) of (face_begin, face_end, vertex_base) rows, the largest item's face count): packed vertices (V, 3)
+    and faces (F, 3) with ids local to their item -> (F,).  The reference's expression, one rounding per operation: the bits of the
+    torch expression on the CPU.  One launch, no host read.  The ids are NOT checked against V on the host (the callers do, see
+    ``faces_in_range``); the kernel writes NaN for a face with an id outside the vertices."""
+    fn = 'face_areas_forward_cuda'
+    sfx, B, F, V, table, _, vs = _sp_mesh(fn, vertices, faces, items)
+    v, f, dev = vertices.detach(), faces.detach(), vertices.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        areas = torch.empty((F,) if table is not None else (B, F), dtype=v.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_face_areas_{sfx}')(_lib.stream_ptr(dev), B, F, V, _lib.ptr(table), _lib.ptr(v), vs[0], vs[1], vs[2],
+                                                         _lib.ptr(f), f.stride(0), f.stride(1), _lib.ptr(areas)), fn)
+    return areas
+
+
+def face_areas_backward_cuda(grad_areas, vertices, faces, items=None):
+    """-> the gradient of the areas per face corner, contiguous (B, F, 3, 3) (packed: (F, 3, 3)), written by plain stores: the
+    reference's autograd expression operation by operation (NaN at a zero-area face, from 0 * inf).  One launch; the sum per
+    vertex is ``vertex_gather_forward_cuda`` in its sum mode."""
+    fn = 'face_areas_backward_cuda'
+    sfx, B, F, V, table, _, vs = _sp_mesh(fn, vertices, faces, items)
+    v, f, dev = vertices.detach(), faces.detach(), vertices.device
+    torch_check(isinstance(grad_areas, torch.Tensor) and grad_areas.dtype == v.dtype, f'{fn}: grad_areas must have the dtype of vertices')
+    _sp_per_face(fn, grad_areas, 'grad_areas', B, F, table is not None, dev)
+    g = grad_areas.detach()
+    gs = (0, g.stride(0)) if table is not None else g.stride()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad = torch.empty((F, 3, 3) if table is not None else (B, F, 3, 3), dtype=v.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_face_areas_backward_{sfx}')(_lib.stream_ptr(dev), B, F, V, _lib.ptr(table), _lib.ptr(v), vs[0],
+                                                                  vs[1], vs[2], _lib.ptr(f), f.stride(0), f.stride(1), _lib.ptr(g),
+                                                                  gs[0], gs[1], _lib.ptr(grad)), fn)
+    return grad
+
+
+def sample_cdf_cuda(areas, items=None):
+    """areas (B, F) float / double (packed: (F,) with ``items``) -> cdf of the same shape in float64: per item the inclusive sums
+    of its areas, widened to float64 and added in float64 in a fixed order (the same bits run after run).  One launch when the
+    largest item fits one tile of the scan (2048 faces), else three; no host read."""
+    fn = 'sample_cdf_cuda'
+    torch_check(isinstance(areas, torch.Tensor) and areas.is_cuda and areas.dtype in (torch.float32, torch.float64),
+                f'{fn}: areas must be a float / double CUDA tensor')
+    dev = areas.device
+    if items is None:
+        torch_check(areas.dim() == 2 and areas.size(0) >= 1 and areas.size(1) >= 1, f'{fn}: areas must be of size (batch_size, num_faces)')
+        B, F, table, max_faces = areas.size(0), areas.size(1), None, areas.size(1)
+    else:
+        table, max_faces = items[0], int(items[1])
+        torch_check(areas.dim() == 1 and areas.size(0) >= 1, f'{fn}: packed areas must be of size (num_faces,)')
+        torch_check(isinstance(table, torch.Tensor) and table.dtype == torch.long and table.device == dev and table.dim() == 2 and
+                    table.size(0) >= 1 and table.size(1) == 3 and table.is_contiguous() and 1 <= max_faces <= areas.size(0),
+                    f'{fn}: items must be (a contiguous long tensor of size (batch_size, 3) on the device of areas, max_faces)')
+        B, F = table.size(0), areas.size(0)
+    a = areas.detach().contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_sample_cdf_workspace(B, max_faces)
+        torch_check(nbytes > 0, f'{fn}: {B} items of {max_faces} faces are more than the scan takes')
+        ws = _lib.workspace(nbytes, dev)
+        cdf = torch.empty(a.shape, dtype=torch.float64, device=dev)
+        _lib.check(getattr(lib, f'kamd_sample_cdf_{_lib.dtype_suffix(a.dtype, fn)}')(
+            _lib.stream_ptr(dev), B, F, max_faces, _lib.ptr(table), _lib.ptr(a), _lib.ptr(cdf), _lib.ptr(ws), nbytes), fn)
+    return cdf
+
+
+def sample_points_forward_cuda(vertices, faces, items, cdf_or_areas, r, uv, face_features=None):
+    """The deterministic part of ``sample_points``: a function of its arguments alone, bit for bit the same on every call.
+
+    vertices (B, V, 3) float / double of any strides, faces (F, 3) long, ``items`` None (or the packed table of
+    ``face_areas_forward_cuda`` with packed vertices (V, 3)); ``cdf_or_areas``: None (the areas are computed), the areas (B, F)
+    float / double (packed: (F,)), or the pair (areas, cdf) of an earlier call (``sample_cdf_cuda``); r (B, N) float64 and uv
+    (B, N, 2) in the dtype of vertices, N >= 1; face_features (B, F, 3, D) in the dtype of vertices, any strides (0 included), or
+    None -> (points (B, N, 3), face_choices (B, N) long (packed: merged ids), features (B, N, D) or None, areas, cdf).
+
+    Launches: areas (1, when not given) + cdf (1 or 3) + sampling (1): at most 5.  No host read, no atomics: capturable."""
+    fn = 'sample_points_forward_cuda'
+    sfx, B, F, V, table, max_faces, vs = _sp_mesh(fn, vertices, faces, items)
+    v, f, dev = vertices.detach(), faces.detach(), vertices.device
+    packed = table is not None
+    torch_check(isinstance(r, torch.Tensor) and r.device == dev and r.dtype == torch.float64 and r.dim() == 2 and r.size(0) == B and
+                r.size(1) >= 1, f'{fn}: r must be a double tensor of size ({B}, num_samples >= 1) on the device of vertices')
+    N = r.size(1)
+    torch_check(isinstance(uv, torch.Tensor) and uv.device == dev and uv.dtype == v.dtype and tuple(uv.shape) == (B, N, 2),
+                f'{fn}: uv must be of size ({B}, {N}, 2) with the dtype and device of vertices')
+    cdf = None
+    if isinstance(cdf_or_areas, (tuple, list)):
+        torch_check(len(cdf_or_areas) == 2, f'{fn}: cdf_or_areas must be None, the areas or the pair (areas, cdf)')
+        areas, cdf = cdf_or_areas
+    else:
+        areas = cdf_or_areas
+    if areas is None:
+        areas = face_areas_forward_cuda(v, f, items)
+    _sp_per_face(fn, areas, 'areas', B, F, packed, dev)
+    areas = areas.detach().contiguous()
+    if cdf is None:
+        cdf = sample_cdf_cuda(areas, items)
+    torch_check(isinstance(cdf, torch.Tensor) and cdf.dtype == torch.float64 and cdf.device == dev and cdf.shape == areas.shape and
+                cdf.is_contiguous(), f'{fn}: cdf must be a contiguous double tensor of the size of areas')
+    D, ff, fs = 0, None, (0, 0, 0, 0)
+    if face_features is not None:
+        torch_check(not packed, f'{fn}: face_features are not taken with packed meshes')
+        torch_check(isinstance(face_features, torch.Tensor) and face_features.device == dev and face_features.dtype == v.dtype and
+                    face_features.dim() == 4 and tuple(face_features.shape[:3]) == (B, F, 3) and face_features.size(3) >= 1,
+                    f'{fn}: face_features must be of size ({B}, {F}, 3, feature_dim >= 1) with the dtype and device of vertices')
+        ff = face_features.detach()
+        D, fs = ff.size(3), ff.stride()
+    rr, uu = r.detach().contiguous(), uv.detach().contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        points = torch.empty((B, N, 3), dtype=v.dtype, device=dev)
+        choices = torch.empty((B, N), dtype=torch.long, device=dev)
+        features = torch.empty((B, N, D), dtype=v.dtype, device=dev) if D > 0 else None
+        _lib.check(getattr(lib, f'kamd_sample_points_{sfx}')(
+            _lib.stream_ptr(dev), B, F, V, N, D, _lib.ptr(table), _lib.ptr(v), vs[0], vs[1], vs[2], _lib.ptr(f), f.stride(0), f.stride(1),
+            _lib.ptr(areas), areas.element_size(), _lib.ptr(cdf), _lib.ptr(rr), _lib.ptr(uu), _lib.ptr(ff), fs[0], fs[1], fs[2], fs[3],
+            _lib.ptr(points), _lib.ptr(choices), _lib.ptr(features)), fn)
+    return points, choices, features, areas, cdf
+
+
+def sample_points_backward_cuda(grad_points, grad_features, faces, items, cdf, uv, face_choices, num_vertices, feature_dim=0):
+    """-> (grad_vertices (B, V, 3) (packed: (V, 3)) or None, grad_face_features (B, F, 3, D) or None), for the cotangents that are
+    not None: ONE launch that recomputes the weights from uv and adds ``w_k g`` to the three vertices and the three feature rows of
+    every sample's face with float atomics, into buffers zero-filled here.  The sums vary from run to run in their last bits (the
+    order of the additions is not fixed).  No host read: capturable."""
+    fn = 'sample_points_backward_cuda'
+    torch_check(isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dim() == 3 and uv.size(2) == 2, f'{fn}: uv must be a CUDA tensor of size (B, N, 2)')
+    sfx = _lib.dtype_suffix(uv.dtype, fn)
+    dev, (B, N), V, D = uv.device, uv.shape[:2], int(num_vertices), int(feature_dim)
+    torch_check(isinstance(faces, torch.Tensor) and faces.device == dev and faces.dim() == 2 and faces.size(1) == 3 and
+                faces.dtype == torch.long and faces.size(0) >= 1, f'{fn}: faces must be a long tensor of size (num_faces >= 1, 3) on the device of uv')
+    F, f = faces.size(0), faces.detach()
+    table = None
+    if items is not None:
+        table = items[0]
+        torch_check(isinstance(table, torch.Tensor) and table.dtype == torch.long and table.device == dev and table.is_contiguous() and
+                    tuple(table.shape) == (B, 3), f'{fn}: items must hold a contiguous long tensor of size ({B}, 3) on the device of uv')
+    torch_check(B >= 1 and N >= 1 and V >= 1 and D >= 0, f'{fn}: every extent must be at least 1')
+    torch_check(isinstance(cdf, torch.Tensor) and cdf.dtype == torch.float64 and cdf.device == dev and cdf.is_contiguous() and
+                tuple(cdf.shape) == ((F,) if table is not None else (B, F)), f'{fn}: cdf must be the contiguous double cdf of the forward')
+    torch_check(isinstance(face_choices, torch.Tensor) and face_choices.dtype == torch.long and face_choices.device == dev and
+                tuple(face_choices.shape) == (B, N), f'{fn}: face_choices must be a long tensor of size ({B}, {N}) on the device of uv')
+    gp = gf = None
+    if grad_points is not None:
+        torch_check(isinstance(grad_points, torch.Tensor) and grad_points.dtype == uv.dtype and grad_points.device == dev and
+                    tuple(grad_points.shape) == (B, N, 3), f'{fn}: grad_points must be of size ({B}, {N}, 3) like uv')
+        gp = grad_points.detach().contiguous()
+    if grad_features is not None:
+        torch_check(table is None and D >= 1, f'{fn}: grad_features need feature_dim >= 1 and a batched mesh')
+        torch_check(isinstance(grad_features, torch.Tensor) and grad_features.dtype == uv.dtype and grad_features.device == dev and
+                    tuple(grad_features.shape) == (B, N, D), f'{fn}: grad_features must be of size ({B}, {N}, {D}) like uv')
+        gf = grad_features.detach().contiguous()
+    uu, choices = uv.detach().contiguous(), face_choices.contiguous()
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_vertices = torch.zeros((V, 3) if table is not None else (B, V, 3), dtype=uv.dtype, device=dev) if gp is not None else None
+        grad_ff = torch.zeros((B, F, 3, D), dtype=uv.dtype, device=dev) if gf is not None else None
+        if gp is not None or gf is not None:
+            _lib.check(getattr(lib, f'kamd_sample_points_backward_{sfx}')(
+                _lib.stream_ptr(dev), B, F, V, N, D if gf is not None else 0, _lib.ptr(table), _lib.ptr(f), f.stride(0), f.stride(1),
+                _lib.ptr(cdf), _lib.ptr(uu), _lib.ptr(choices), _lib.ptr(gp), _lib.ptr(gf),
+                _lib.ptr(grad_vertices), _lib.ptr(grad_ff)), fn)
+    return grad_vertices, grad_ff
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
                               vertex_corners_cuda=vertex_corners_cuda,
                               vertex_gather_forward_cuda=vertex_gather_forward_cuda,
                               vertex_gather_backward_cuda=vertex_gather_backward_cuda,
+                              face_areas_forward_cuda=face_areas_forward_cuda,
+                              face_areas_backward_cuda=face_areas_backward_cuda,
+                              sample_cdf_cuda=sample_cdf_cuda,
+                              sample_points_forward_cuda=sample_points_forward_cuda,
+                              sample_points_backward_cuda=sample_points_backward_cuda,
                               subdivide_trianglemesh_cuda=subdivide_trianglemesh_cuda,
                               trianglemesh_loop_forward_cuda=trianglemesh_loop_forward_cuda,
                               trianglemesh_loop_backward_cuda=trianglemesh_loop_backward_cuda,

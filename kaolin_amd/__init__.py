@@ -12,7 +12,8 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
     kaolin_amd.ops.mesh         subdivide_tetmesh (HIP edge-midpoint pipeline), inverse_vertices_offset, check_sign,
                                 subdivide_trianglemesh (Loop subdivision with a per-vertex alpha, HIP pipeline),
                                 average_face_vertex_features, compute_vertex_normals, vertex_tangents (one deterministic HIP gather
-                                over cached vertex -> corner lists, the bits of the reference's CPU result), unindex_vertices_by_faces
+                                over cached vertex -> corner lists, the bits of the reference's CPU result), unindex_vertices_by_faces,
+                                face_areas, sample_points and their packed forms (HIP areas, float64 scan, search-and-blend)
     kaolin_amd.ops.spc          the SPC core: scan_octrees, generate_points, unbatched_query, to_dense, unbatched_points_to_octree (HIP),
                                 conv3d / conv_transpose3d and their layers (HIP neighbour map + MFMA gather-GEMM)
     kaolin_amd.ops.spc.bf_recon bf_recon, fuseBF, the empty-aware unbatched_query (HIP operators of csrc/spc_bf.hip)

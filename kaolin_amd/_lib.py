@@ -155,6 +155,15 @@ SIGNATURES.update({
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_vertex_gather_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] + [_i64] * 4 + [_vp, _vp, _i, _vp])
     SIGNATURES[f'kamd_vertex_gather_backward_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] + [_i64] * 3 + [_vp, _i, _i64, _i64, _vp, _i, _vp])
+SIGNATURES['kamd_sample_cdf_workspace'] = (_sz, [_i64, _i64])
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_face_areas_{_t}'] = (_i, [_vp] + [_i64] * 3 + [_vp, _vp] + [_i64] * 3 + [_vp, _i64, _i64, _vp])
+    SIGNATURES[f'kamd_face_areas_backward_{_t}'] = (_i, [_vp] + [_i64] * 3 + [_vp, _vp] + [_i64] * 3 + [_vp, _i64, _i64, _vp, _i64,
+                                                                                                      _i64, _vp])
+    SIGNATURES[f'kamd_sample_cdf_{_t}'] = (_i, [_vp] + [_i64] * 3 + [_vp] * 4 + [_sz])
+    SIGNATURES[f'kamd_sample_points_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp, _vp] + [_i64] * 3 + [_vp, _i64, _i64, _vp, _i] +
+                                              [_vp] * 4 + [_i64] * 4 + [_vp] * 3)
+    SIGNATURES[f'kamd_sample_points_backward_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp, _vp, _i64, _i64] + [_vp] * 7)
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):

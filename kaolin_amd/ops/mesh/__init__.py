@@ -2,12 +2,14 @@
 subdivision the voxelizer's definition rests on; the tetrahedral-mesh operators of tetmesh.py (subdivide_tetmesh on a HIP
 edge-midpoint pipeline); subdivide_trianglemesh of trianglemesh.py (Loop subdivision with a per-vertex alpha, on HIP); and the
 per-vertex averages of vertex_features.py (average_face_vertex_features, compute_vertex_normals, vertex_tangents on a deterministic
-HIP gather, unindex_vertices_by_faces)."""
+HIP gather, unindex_vertices_by_faces); and face_areas / sample_points with their packed forms of sampling.py (a HIP areas, scan and
+search-and-blend pipeline)."""
 import torch
 
 __all__ = ['index_vertices_by_faces', 'face_normals', 'check_sign', 'adjacency_matrix', 'uniform_laplacian',
            'subdivide_tetmesh', 'inverse_vertices_offset', 'subdivide_trianglemesh', 'average_face_vertex_features',
-           'compute_vertex_normals', 'unindex_vertices_by_faces', 'vertex_tangents']
+           'compute_vertex_normals', 'unindex_vertices_by_faces', 'vertex_tangents', 'face_areas', 'packed_face_areas',
+           'sample_points', 'packed_sample_points']
 
 
 def index_vertices_by_faces(vertices_features, faces):
@@ -181,3 +183,5 @@ from .trianglemesh import subdivide_trianglemesh  # noqa: E402
 from . import vertex_features  # noqa: E402
 from .vertex_features import (average_face_vertex_features, compute_vertex_normals, unindex_vertices_by_faces,  # noqa: E402
                               vertex_tangents)
+from . import sampling  # noqa: E402
+from .sampling import face_areas, packed_face_areas, sample_points, packed_sample_points  # noqa: E402
