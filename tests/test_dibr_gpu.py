@@ -769,8 +769,10 @@ def test_box_edges_within_two_thousandths_of_a_pixel_centre(dtype, H, W, big_x):
 @pytest.mark.parametrize('n_big', [40, 2500])
 def test_fused_backward_with_image_sized_faces_equals_the_composition(n_big):
     """Faces whose enlarged box spans more than 8 x 8 soft tiles collect their soft-mask gradient in per-XCD partial sums that the
-    rasterizer's backward launch folds in (csrc/tile_lists.h, WORK_BIGHASH_WORD): with 40 such faces the table is in use, with
-    2 500 it is over its limit and left alone.  Either way the fused operator's vertex gradient equals the composition's
+    rasterizer's backward launch folds in (csrc/tile_lists.h, WORK_BIGHASH_WORD).  A random face of size 2.2 spans 9 soft tile columns
+    or rows in ~6 % of the draws: 2 of the 40 and 158 of the 2 500 are on the table, which is in use both times (2 500 do NOT take
+    it over BIG_HASH_MAX, as this docstring once said, and they cover every pixel, so no soft hit is left; the case over the limit is
+    hot_slivers in tests/weighted_sum_dibr_cases.py).  Either way the fused operator's vertex gradient equals the composition's
     (rasterize + dibr_soft_mask: the stand-alone soft-mask backward never uses the table), and a second backward through the
     retained graph gives the same again (the partial sums are left cleared)."""
     import kaolin_amd as kal

@@ -4,7 +4,11 @@ metrics.render.weighted_sum(feat, G1, soft, G2) on the outputs of one dibr_raste
 DIB-R backward kernels read G1 / G2 and scale them by the loss' gradient where they read a gradient
 (kamd_dibr_weighted_sum_backward_*).  Every case is compared with the loss written in torch, (feat * G1).sum() +
 (soft * G2).sum(), which materialises both gradients and runs the rasterizer's own backward: the gradient terms are the
-same, only the order of the float atomics differs (same_sum_other_order, as the DIB-R backward tests compare)."""
+same, only the order of the float atomics differs (same_sum_other_order, as the DIB-R backward tests compare).
+
+That yardstick runs the same backward kernels in their plain instantiation, at D = 3 and on whole tiles: the comparison with the CPU
+oracle, element by element, at every D the launchers switch on, on partial tiles, 1 / 8 / 9 / 17 views and with the hot-face table in
+use and over its limit lives in tests/test_weighted_sum_dibr_oracle_gpu.py."""
 import math
 
 import pytest
