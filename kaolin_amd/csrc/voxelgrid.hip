@@ -60,13 +60,20 @@ __device__ __forceinline__ T vox_edge2(const T* a, const T* b) {
   const T dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
   return (dx * dx + dy * dy) + dz * dz;
 }
-// t = {v1, v2, v3}; true when the triangle must be subdivided
+// torch.min / torch.max propagate NaN: so do these
+template <typename T>
+__device__ __forceinline__ T vox_nan_min(T a, T b) { return (a != a || a < b) ? a : b; }
+template <typename T>
+__device__ __forceinline__ T vox_nan_max(T a, T b) { return (a != a || a > b) ? a : b; }
+// t = {v1, v2, v3}; true when the triangle must be subdivided.  The reference takes torch.max of the three squared edges
+// (kaolin/ops/mesh/trianglemesh.py:420-428): a NaN edge makes the maximum NaN, and NaN > thr is false -- a face with a NaN
+// vertex is never subdivided, whichever of its corners that is
 template <typename T>
 __device__ __forceinline__ bool vox_keep(const T* t, T thr) {
   T m = vox_edge2(t, t + 3);
   const T e2 = vox_edge2(t + 3, t + 6), e3 = vox_edge2(t + 6, t);
-  if (e2 > m) m = e2;
-  if (e3 > m) m = e3;
+  m = vox_nan_max<T>(m, e2);
+  m = vox_nan_max<T>(m, e3);
   return m > thr;
 }
 // mids = {v4 = (v1+v3)/2, v5 = (v1+v2)/2, v6 = (v2+v3)/2}
@@ -92,11 +99,7 @@ __device__ __forceinline__ void vox_child(const T* t, const T* m, int c, T* out)
 }
 
 // origin (B,3) / scale (B) of the reference's normalisation (trianglemesh.py:84-96) when the caller gives none:
-// origin = per-mesh minimum, scale = largest extent above the origin.  torch.min / torch.max propagate NaN: so do these.
-template <typename T>
-__device__ __forceinline__ T vox_nan_min(T a, T b) { return (a != a || a < b) ? a : b; }
-template <typename T>
-__device__ __forceinline__ T vox_nan_max(T a, T b) { return (a != a || a > b) ? a : b; }
+// origin = per-mesh minimum, scale = largest extent above the origin, reduced with vox_nan_min / vox_nan_max (NaN propagates).
 constexpr int VOX_NP = 32;  // partial extents per mesh
 // scratch layout (scalars): [B*4] origin xyz + scale | [B*VOX_NP*6] partial min xyz, max xyz
 template <typename T>

@@ -25,13 +25,12 @@ def _edge2(a, b):
     return (sq[:, 0] + sq[:, 1]) + sq[:, 2]
 
 
-def subdivide_points(vertices, faces, resolution):
-    """(V,3) normalised vertices + (F,3) faces -> (P,3) array holding every original vertex and every
-    midpoint the reference's subdivision generates (duplicates allowed: only the set matters)."""
+def subdivision_rounds(vertices, faces, resolution):
+    """Yields, round by round, the midpoints (v4, v5, v6) of the triangles the reference keeps in that round; ends with the
+    first round that keeps none.  (np.maximum propagates NaN as torch.max does: a triangle with a NaN edge is never kept.)"""
     assert resolution > 1
     dt = vertices.dtype.type
     thr = dt(((resolution - 1) / (resolution ** 2)) ** 2)
-    pts = [vertices]
     v1, v2, v3 = vertices[faces[:, 0]], vertices[faces[:, 1]], vertices[faces[:, 2]]
     two = dt(2)
     while v1.shape[0] > 0:
@@ -41,16 +40,26 @@ def subdivide_points(vertices, faces, resolution):
             break
         v1, v2, v3 = v1[keep], v2[keep], v3[keep]
         v4, v5, v6 = (v1 + v3) / two, (v1 + v2) / two, (v2 + v3) / two
-        pts += [v4, v5, v6]
+        yield v4, v5, v6
         v1, v2, v3 = (np.concatenate((v1, v2, v4, v3)), np.concatenate((v4, v5, v5, v4)),
                       np.concatenate((v5, v6, v6, v6)))
+
+
+def subdivide_points(vertices, faces, resolution):
+    """(V,3) normalised vertices + (F,3) faces -> (P,3) array holding every original vertex and every
+    midpoint the reference's subdivision generates (duplicates allowed: only the set matters)."""
+    pts = [vertices]
+    for mids in subdivision_rounds(vertices, faces, resolution):
+        pts += mids
     return np.concatenate(pts)
 
 
 def points_to_dense(points, resolution, dtype):
-    idx = np.rint(points * points.dtype.type(resolution - 1)).astype(np.int64)
-    ok = ((idx >= 0) & (idx <= resolution - 1)).all(axis=1)
-    idx = idx[ok]
+    # rows with a NaN or infinite coordinate mark nothing (the reference's cast sends them outside [0, res-1]): dropped before
+    # the integer cast, which is undefined for them
+    points = points[np.isfinite(points).all(axis=1)]
+    idx = np.rint(points * points.dtype.type(resolution - 1))
+    idx = idx[((idx >= 0) & (idx <= resolution - 1)).all(axis=1)].astype(np.int64)
     grid = np.zeros((resolution,) * 3, dtype=dtype)
     grid[idx[:, 0], idx[:, 1], idx[:, 2]] = 1
     return grid
