@@ -117,10 +117,16 @@ def test_gpu_vs_reference_golden(gold, tag, dn):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('dtype', [torch.float, torch.double])
-@pytest.mark.parametrize('N,F', [(1, 1), (777, 3), (5000, 1300), (64, 20480), (30000, 5120)])
+@pytest.mark.parametrize('N,F', [(1, 1), (777, 3), (5000, 1300), (64, 20480), (30000, 5120)] +
+                         # the forward's edges: the LDS tile of 64 faces, one -> several face splits at 8 tiles, the re-seed
+                         # threshold F <= 512; queries on either side of a wavefront and of a workgroup
+                         [(n, f) for n in (63, 64, 65, 255, 256, 257) for f in (63, 64, 65, 511, 512, 513, 1025)])
 def test_gpu_vs_oracle(dtype, N, F):
-    """dist / face_idx / dist_type bit-exact vs the oracle (same IEEE operations incl. the 1/sqrt pin);
-    gradients 1e-5 relative (atomic order)."""
+    """dist / face_idx / dist_type bit-exact vs the oracle (same IEEE operations incl. the 1/sqrt pin); gradients per element: every
+    point's terms within K u M of float64 autograd of the stored region, g_points equal to them, every face value within
+    gamma_(n-1) sum|term| of their sum with its own n (tests/triangle_distance_gradient_cases.py)."""
+    import triangle_distance_gradient_cases as C
+    gpu_backward = C.gpu_backward
     from kaolin_amd.utils.testing import geodesic_sphere
     torch.manual_seed(N + F)
     if F in (20480, 5120):
@@ -137,9 +143,16 @@ def test_gpu_vs_oracle(dtype, N, F):
     assert torch.equal(dist.detach().cpu(), d_ref)
     g = torch.rand(N, dtype=dtype)
     dist.backward(g.cuda())
-    gp, gf = oracle.triangle_distance_backward(g, pts, fv, i_ref, t_ref)
-    assert float((a.grad.cpu() - gp).abs().max()) <= 1e-5 * max(float(gp.abs().max()), 1e-30)
-    assert float((b.grad.cpu() - gf).abs().max()) <= 1e-5 * max(float(gf.abs().max()), 1e-30)
+    # the shim driven directly: terms against float64 autograd, g_points == terms, g_faces against the terms' sum
+    C.check_operator(gpu_backward, g, pts, fv, i_ref, t_ref, dtype, f'N={N} F={F} {dtype}')
+    # the autograd function's result: the same terms (bit for bit) and the same bound
+    t_p, t_f = C.operator_terms(gpu_backward, g, pts, fv, i_ref, t_ref)
+    assert torch.equal(a.grad.cpu(), t_p)
+    s, _ = C.accumulation_share(b.grad.cpu(), t_f, i_ref, t_ref, C.U[dtype])
+    assert C.accumulation_within(s), f'{int((~(s <= 1)).sum())} face values outside gamma_(n-1) sum|term|'
+    # ... which the pinned oracle's terms equal, so its double sum meets the bound too
+    o_p, o_f = C.operator_terms(oracle.triangle_distance_backward, g, pts, fv, i_ref, t_ref)
+    assert torch.equal(t_p, o_p) and torch.equal(t_f, o_f)
 
 
 def _near(a, b, scale2, ulps=32):
