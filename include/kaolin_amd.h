@@ -1567,6 +1567,44 @@ int kamd_sample_points_backward_f64(void* stream, int64_t B, int64_t F, int64_t 
                                     double* grad_vertices, double* grad_face_features);
 
 /* ------------------------------------------------------------------------- */
+/* ops.gaussians.transform_gaussians / transform_shs                           */
+/* (csrc/gaussian_transform.hip; the reference is pure torch, kaolin/ops/      */
+/* gaussians/transforms.py: these entry points exist only on our side).  N     */
+/* Gaussians; every tensor contiguous.  transform: the first of the matrices,  */
+/* transform_stride ELEMENTS apart (0: one matrix shared by all) with rows     */
+/* transform_row_stride apart: (N or 1, 4, 4) is stride 16 or 0 and row 4.     */
+/* flags: 1 = quaternions are xyzw (else wxyz), 2 = log scales, 4 = the        */
+/* rotation is GIVEN: the matrices are R itself, (N or 1, 3, 3) = stride 9 or  */
+/* 0 and row 3, and there is no geometry (transform_shs).  Otherwise A =       */
+/* matrix[:3, :3], R = A / its column norms.                                   */
+/* forward: positions (N,3), orientations (N,4), scales (N,3) and their three  */
+/*   outputs are all given or all NULL; sh / new_sh (N, (degree + 1)^2, 3),    */
+/*   0 <= degree <= 3, both given or both NULL.                                */
+/* backward: every (grad_new_x, grad_x) pair is given or NULL, only the given  */
+/*   ones are computed; orientations (the forward's input) is needed for       */
+/*   grad_orientations.  No gradient with respect to the transform.            */
+/* One launch each, no workspace, no atomics, no host read: capturable, and    */
+/* the same bits on every call; the shared and the per-Gaussian transform give */
+/* the same bits for the same matrix.  The file states the arithmetic.         */
+/* ------------------------------------------------------------------------- */
+int kamd_gaussian_transform_forward_f32(void* stream, int64_t N, int degree, int flags, const float* transform, int64_t transform_stride,
+                                        int64_t transform_row_stride, const float* positions, const float* orientations,
+                                        const float* scales, const float* sh, float* new_positions, float* new_orientations,
+                                        float* new_scales, float* new_sh);
+int kamd_gaussian_transform_forward_f64(void* stream, int64_t N, int degree, int flags, const double* transform, int64_t transform_stride,
+                                        int64_t transform_row_stride, const double* positions, const double* orientations,
+                                        const double* scales, const double* sh, double* new_positions, double* new_orientations,
+                                        double* new_scales, double* new_sh);
+int kamd_gaussian_transform_backward_f32(void* stream, int64_t N, int degree, int flags, const float* transform, int64_t transform_stride,
+                                         int64_t transform_row_stride, const float* orientations, const float* grad_new_positions,
+                                         const float* grad_new_orientations, const float* grad_new_scales, const float* grad_new_sh,
+                                         float* grad_positions, float* grad_orientations, float* grad_scales, float* grad_sh);
+int kamd_gaussian_transform_backward_f64(void* stream, int64_t N, int degree, int flags, const double* transform, int64_t transform_stride,
+                                         int64_t transform_row_stride, const double* orientations, const double* grad_new_positions,
+                                         const double* grad_new_orientations, const double* grad_new_scales, const double* grad_new_sh,
+                                         double* grad_positions, double* grad_orientations, double* grad_scales, double* grad_sh);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

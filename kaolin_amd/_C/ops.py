@@ -2232,8 +2232,104 @@ def sample_points_backward_cuda(grad_points, grad_features, faces, items, cdf, u
     return grad_vertices, grad_ff
 
 
+# ---- kaolin._C.ops.gaussians: transform_gaussians / transform_shs on csrc/gaussian_transform.hip (no reference counterpart: pure torch
+# there).  One launch per call, nothing reads back or synchronises: the operators capture into a graph.
+def _gt_args(fn, named, transform, rotation_given):
+    """named: [(name, tensor or None, trailing shape)]; every tensor float32 / float64 on the GPU of `transform`, N rows each
+    -> (suffix, N, transform made contiguous, its stride in elements, its row stride, the tensors made contiguous)"""
+    torch_check(torch.is_tensor(transform) and transform.is_cuda, f'{fn}: transform must be a CUDA tensor')
+    sfx = _lib.dtype_suffix(transform.dtype, fn)
+    side = 3 if rotation_given else 4
+    torch_check(transform.dim() == 3 and tuple(transform.shape[1:]) == (side, side),
+                f'{fn}: transform must of size {{num_gaussians or 1, {side}, {side}}}')
+    given = [(name, t, tail) for name, t, tail in named if t is not None]
+    torch_check(len(given) > 0, f'{fn}: nothing to transform')
+    n = given[0][1].size(0) if given[0][1].dim() else -1
+    out = []
+    for name, t, tail in named:
+        if t is None:
+            out.append(None)
+            continue
+        torch_check(t.is_cuda and t.device == transform.device, f'{fn}: {name} must be a CUDA tensor on the device of transform')
+        torch_check(t.dtype == transform.dtype, f'{fn}: expected {name} to have the scalar type of transform')
+        torch_check(t.dim() == 1 + len(tail) and t.size(0) == n and all(a == b or b is None for a, b in zip(t.shape[1:], tail)),
+                    f'{fn}: {name} must of size {{num_gaussians, {", ".join("S" if b is None else str(b) for b in tail)}}}')
+        out.append(t.detach().contiguous())
+    torch_check(transform.size(0) in (1, n), f'{fn}: transform must of size {{num_gaussians or 1, {side}, {side}}}')
+    tf = transform.detach().contiguous()
+    return sfx, n, tf, (side * side if tf.size(0) == n and n != 1 else 0), side, out
+
+
+def _gt_degree(fn, sh):
+    if sh is None:
+        return 0
+    degree = {1: 0, 4: 1, 9: 2, 16: 3}.get(sh.size(1))
+    torch_check(degree is not None, f'{fn}: sh must hold 1, 4, 9 or 16 coefficients, got {sh.size(1)}')
+    return degree
+
+
+def _gt_flags(use_log_scales, use_xyzw, rotation_given):
+    return (1 if use_xyzw else 0) | (2 if use_log_scales else 0) | (4 if rotation_given else 0)
+
+
+def transform_gaussians_forward_cuda(positions, orientations, scales, transform, sh_coeff=None, use_log_scales=False, use_xyzw=False,
+                                     rotation_given=False):
+    """positions (N, 3), orientations (N, 4), scales (N, 3): all three or all None; sh_coeff (N, 1 | 4 | 9 | 16, 3) or None;
+    transform (N or 1, 4, 4), or with ``rotation_given`` the rotations themselves, (N or 1, 3, 3), and no geometry
+    -> (new_positions, new_orientations, new_scales, new_sh_coeff), None where the input is.  Inputs that are not contiguous are
+    copied.  N = 0 launches nothing."""
+    fn = 'transform_gaussians_forward_cuda'
+    geometry = [positions is not None, orientations is not None, scales is not None]
+    torch_check(all(geometry) or not any(geometry), f'{fn}: positions, orientations and scales are given together or not at all')
+    torch_check(not (rotation_given and any(geometry)), f'{fn}: a given rotation transforms sh_coeff only')
+    sfx, n, tf, stride, row, (pos, ori, scl, sh) = _gt_args(
+        fn, [('positions', positions, (3,)), ('orientations', orientations, (4,)), ('scales', scales, (3,)),
+             ('sh_coeff', sh_coeff, (None, 3))], transform, rotation_given)
+    degree = _gt_degree(fn, sh)
+    dev = tf.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        outs = [None if t is None else torch.empty_like(t) for t in (pos, ori, scl, sh)]
+        if n > 0:
+            _lib.check(getattr(lib, f'kamd_gaussian_transform_forward_{sfx}')(
+                _lib.stream_ptr(dev), n, degree, _gt_flags(use_log_scales, use_xyzw, rotation_given), _lib.ptr(tf), stride, row,
+                _lib.ptr(pos), _lib.ptr(ori), _lib.ptr(scl), _lib.ptr(sh), *(_lib.ptr(t) for t in outs)), fn)
+    return tuple(outs)
+
+
+def transform_gaussians_backward_cuda(grad_new_positions, grad_new_orientations, grad_new_scales, grad_new_sh_coeff, orientations,
+                                      transform, use_log_scales=False, use_xyzw=False, rotation_given=False,
+                                      need=(True, True, True, True)):
+    """The gradients of the forward's outputs (any of them None) -> (grad_positions, grad_orientations, grad_scales, grad_sh_coeff):
+    entry k is computed when ``need[k]`` and its output's gradient is given, else None.  ``orientations`` is the forward's input
+    (needed for grad_orientations only).  No gradient with respect to ``transform``."""
+    fn = 'transform_gaussians_backward_cuda'
+    grads = [grad_new_positions, grad_new_orientations, grad_new_scales, grad_new_sh_coeff]
+    grads = [g if k else None for g, k in zip(grads, need)]
+    if all(g is None for g in grads):
+        return (None, None, None, None)
+    torch_check(not (rotation_given and any(g is not None for g in grads[:3])), f'{fn}: a given rotation transforms sh_coeff only')
+    torch_check(grads[1] is None or orientations is not None, f'{fn}: grad_orientations needs the orientations')
+    sfx, n, tf, stride, row, (gp, go, gs, gsh, ori) = _gt_args(
+        fn, [('grad_new_positions', grads[0], (3,)), ('grad_new_orientations', grads[1], (4,)), ('grad_new_scales', grads[2], (3,)),
+             ('grad_new_sh_coeff', grads[3], (None, 3)), ('orientations', orientations if grads[1] is not None else None, (4,))],
+        transform, rotation_given)
+    degree = _gt_degree(fn, gsh)
+    dev = tf.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        outs = [None if t is None else torch.empty_like(t) for t in (gp, go, gs, gsh)]
+        if n > 0:
+            _lib.check(getattr(lib, f'kamd_gaussian_transform_backward_{sfx}')(
+                _lib.stream_ptr(dev), n, degree, _gt_flags(use_log_scales, use_xyzw, rotation_given), _lib.ptr(tf), stride, row,
+                _lib.ptr(ori), _lib.ptr(gp), _lib.ptr(go), _lib.ptr(gs), _lib.ptr(gsh), *(_lib.ptr(t) for t in outs)), fn)
+    return tuple(outs)
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
+gaussians = _types.SimpleNamespace(transform_gaussians_forward_cuda=transform_gaussians_forward_cuda,
+                                   transform_gaussians_backward_cuda=transform_gaussians_backward_cuda)
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,
                               vertex_corners_cuda=vertex_corners_cuda,
                               vertex_gather_forward_cuda=vertex_gather_forward_cuda,

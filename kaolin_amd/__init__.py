@@ -17,7 +17,10 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
     kaolin_amd.ops.spc          the SPC core: scan_octrees, generate_points, unbatched_query, to_dense, unbatched_points_to_octree (HIP),
                                 conv3d / conv_transpose3d and their layers (HIP neighbour map + MFMA gather-GEMM)
     kaolin_amd.ops.spc.bf_recon bf_recon, fuseBF, the empty-aware unbatched_query (HIP operators of csrc/spc_bf.hip)
-    kaolin_amd.ops.gaussians    sample_points_in_volume: fills a shell of Gaussian splats (also as kaolin_amd.ops.gaussian)
+    kaolin_amd.ops.gaussians    sample_points_in_volume: fills a shell of Gaussian splats (also as kaolin_amd.ops.gaussian);
+                                transform_gaussians, transform_shs: a rigid / similarity transform of a splat model with its SH
+                                rotated (one fused HIP kernel per direction, exact Ivanic-Ruedenberg coefficients)
+    kaolin_amd.math.quat        quat_from_rot33, quat_mul, quat_unit (xyzw, plain torch): what the transforms need of kaolin.math
     kaolin_amd.rep              Spc, the structured point cloud data class
     kaolin_amd.ops.voxelgrid    fill (HIP flood fill over bit grids), downsample, extract_surface, extract_odms, project_odms
     kaolin_amd.metrics.voxelgrid  iou
@@ -34,7 +37,7 @@ existing notebooks/tests written against the reference import it unchanged.
 import sys
 
 from . import _C  # noqa: F401
-from . import io, metrics, ops, render, rep, utils  # noqa: F401
+from . import io, math, metrics, ops, render, rep, utils  # noqa: F401
 from . import distributed  # noqa: F401
 
 __version__ = '0.1.0'

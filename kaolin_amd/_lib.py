@@ -164,6 +164,9 @@ for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_sample_points_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp, _vp] + [_i64] * 3 + [_vp, _i64, _i64, _vp, _i] +
                                               [_vp] * 4 + [_i64] * 4 + [_vp] * 3)
     SIGNATURES[f'kamd_sample_points_backward_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp, _vp, _i64, _i64] + [_vp] * 7)
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_gaussian_transform_forward_{_t}'] = (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64] + [_vp] * 8)
+    SIGNATURES[f'kamd_gaussian_transform_backward_{_t}'] = (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64] + [_vp] * 9)
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):
