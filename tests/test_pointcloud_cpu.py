@@ -112,7 +112,13 @@ def spc_case(name, level, point_dtype, D, feature_dtype):
 def check_spc(name, level, device, point_dtype=torch.float32, D=3, feature_dtype=torch.float32, strided=False):
     """The octree against the oracle and against unbatched_points_to_octree(quantize_points(...)); integer features bit-equal to
     the oracle, float features within its derived bound.  -> (spc, share of the bound used or None)"""
-    pts, feats, orc = spc_case(name, level, point_dtype, D, feature_dtype)
+    return check_spc_case(spc_case(name, level, point_dtype, D, feature_dtype), name, level, device, strided)
+
+
+def check_spc_case(case, name, level, device, strided=False):
+    """check_spc on a prepared (points, features or None, oracle) triple of CPU tensors (tests/pointcloud_boundary_cases.py)"""
+    pts, feats, orc = case
+    D = 0 if feats is None else feats.shape[1]
     p, f = pts.to(device), None if feats is None else feats.to(device)
     if strided:                                 # column slices of wider tensors
         wide = torch.zeros((p.shape[0], 5), dtype=p.dtype, device=device)
