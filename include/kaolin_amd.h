@@ -1605,6 +1605,24 @@ int kamd_gaussian_transform_backward_f64(void* stream, int64_t N, int degree, in
                                          double* grad_positions, double* grad_orientations, double* grad_scales, double* grad_sh);
 
 /* ------------------------------------------------------------------------- */
+/* ops.pointcloud.farthest_point_sampling (csrc/fps.hip; the reference runs    */
+/* NVIDIA Warp kernels, kaolin/ops/pointcloud.py:98-535: these entry points    */
+/* exist only on our side).  points (B, N, 3) float32 contiguous, 0 <= k <= N  */
+/* -> out (B, k) int64, by the rule the file states: the same indices on every */
+/* call and on both paths.  path: 0 = choose (block up to                      */
+/* kamd_fps_block_limit() points, rounds above), 1 = block: one workgroup per  */
+/* cloud with the points in registers, 2 = rounds: one launch per selected     */
+/* point, B <= 65535.  A forced path that does not apply is an error status.   */
+/* workspace: kamd_fps_workspace(B, N, k, path) bytes (pure host arithmetic; 0 */
+/* where the block path runs), 16-byte aligned, not initialised.  No host      */
+/* read, no synchronisation, no atomics: capturable.  k == 0 or B == 0         */
+/* launches nothing.                                                           */
+/* ------------------------------------------------------------------------- */
+int kamd_fps_block_limit(void);
+size_t kamd_fps_workspace(int B, int N, int k, int path);
+int kamd_fps_f32(void* stream, int B, int N, int k, const float* points, int64_t* out, void* workspace, int path);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -2326,6 +2326,33 @@ def transform_gaussians_backward_cuda(grad_new_positions, grad_new_orientations,
     return tuple(outs)
 
 
+_FPS_PATHS = {None: 0, 'block': 1, 'rounds': 2}
+
+
+def farthest_point_sampling_cuda(points, k, path=None):
+    """points (B, N, 3) float32 on the GPU, 0 <= k <= N -> (B, k) int64 indices on the same device, by the rule of csrc/fps.hip
+    (no reference operator: the reference runs Warp kernels).  ``path``: None = by size, 'block' = one workgroup per cloud
+    (N <= ``kamd_fps_block_limit()``), 'rounds' = one launch per selected point.  Nothing reads back or synchronises: the call
+    captures into a graph.  k == 0 or B == 0 launches nothing."""
+    fn = 'farthest_point_sampling_cuda'
+    torch_check(points.is_cuda, f'{fn}: points must be a CUDA tensor')
+    torch_check(points.dim() == 3 and points.size(2) == 3, f'{fn}: points must of size {{batch_size, num_points, 3}}')
+    torch_check(points.dtype == torch.float32, f'{fn}: points must be float')
+    B, N, k = points.size(0), points.size(1), int(k)
+    torch_check(0 <= k <= N, f'{fn}: k must satisfy 0 <= k <= num_points')
+    torch_check(N < 2 ** 31 and B < 2 ** 31, f'{fn}: a dimension exceeds the 32-bit range')
+    torch_check(path in _FPS_PATHS, f'{fn}: path must be None, "block" or "rounds"')
+    p = points.detach().contiguous()
+    dev = p.device
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.empty((B, k), dtype=torch.int64, device=dev)
+        if out.numel() > 0:
+            ws = _lib.workspace(lib.kamd_fps_workspace(B, N, k, _FPS_PATHS[path]), dev)
+            _lib.check(lib.kamd_fps_f32(_lib.stream_ptr(dev), B, N, k, _lib.ptr(p), _lib.ptr(out), _lib.ptr(ws), _FPS_PATHS[path]), fn)
+    return out
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
 gaussians = _types.SimpleNamespace(transform_gaussians_forward_cuda=transform_gaussians_forward_cuda,

@@ -167,6 +167,11 @@ for _t in ('f32', 'f64'):
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_gaussian_transform_forward_{_t}'] = (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64] + [_vp] * 8)
     SIGNATURES[f'kamd_gaussian_transform_backward_{_t}'] = (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64] + [_vp] * 9)
+SIGNATURES.update({
+    'kamd_fps_block_limit': (_i, []),
+    'kamd_fps_workspace': (_sz, [_i, _i, _i, _i]),
+    'kamd_fps_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i]),
+})
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):

@@ -1,6 +1,7 @@
 from . import mesh  # noqa: F401
 from . import conversions  # noqa: F401
 from . import voxelgrid  # noqa: F401
+from . import pointcloud  # noqa: F401
 from . import spc  # noqa: F401
 from . import random  # noqa: F401
 from . import gaussians  # noqa: F401
