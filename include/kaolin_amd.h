@@ -1502,6 +1502,56 @@ int kamd_vertex_gather_backward_f64(void* stream, int64_t B, int64_t F, int64_t 
                                     int64_t faces_stride_f, int64_t faces_stride_k, const int32_t* offsets, int mean, double* grad);
 
 /* ------------------------------------------------------------------------- */
+/* ops.gcn: sparse (M, N) times batched dense (B, N, P) as a gather over lists */
+/* (csrc/gcn.hip: sparse_bmm, normalize_adj, GraphConv; the reference calls    */
+/* torch.sparse.mm on a transposed copy, these entry points exist only on our  */
+/* side).  M, N, nnz >= 1 and < 2^31 - 1.                                      */
+/* lists_build: indices (2, nnz) int64 and values (nnz) of value_bytes 4 or 8, */
+/*   both with element strides -> the row lists row_offsets (M + 1), cols      */
+/*   (nnz), row_vals (nnz) and the column lists col_offsets (N + 1), rows      */
+/*   (nnz), col_vals (nnz), int32 / the values' type, contiguous: the entries  */
+/*   of a row (a column) in COO order (two stable keys-only sorts over the low  */
+/*   ceil(log2 M) / ceil(log2 N) bits of (e << 32) | id, a binary search per   */
+/*   offset).  *host_bad = the number of entries outside the matrix (they are  */
+/*   filed under (0, 0): the caller raises) -- the ONE host read; the call     */
+/*   synchronises the stream.  workspace: kamd_gcn_lists_workspace(M, N, nnz)  */
+/*   bytes (0: extents out of range).                                          */
+/* aggregate_*: lists of R rows over S source rows + x (B, S, P) with element  */
+/*   strides (0 allowed) -> out (B, R, P) contiguous: per element the          */
+/*   sequential sum over the row's entries in list order from +0 of            */
+/*   val * x[b, idx, p], one rounded multiply and one rounded add each;        */
+/*   src_norm (S) != NULL: every term reads x / src_norm[idx]; normalize != 0: */
+/*   the sum is divided ONCE by the row's sequential sum of values (0 / 0 =    */
+/*   NaN), written to norm_out (R) when not NULL; addend (B, R, P) with        */
+/*   element strides != NULL: added last.  Groups of G lanes per row, G = the  */
+/*   smallest power of two >= min(ceil(B P / vec), 64), vec = 4 where P % 4 == */
+/*   0 and rows are 16-byte aligned, else 1.  One launch, no atomics, no host  */
+/*   read.                                                                     */
+/* row_sums_*: norm (M) = the sequential sum of every row's values.            */
+/* scale_values_*: out[e] = values[e] / norm[rows[e]] in the COO's own order   */
+/*   (rows = the first row of indices, with its element stride).               */
+/* ------------------------------------------------------------------------- */
+size_t kamd_gcn_lists_workspace(int64_t M, int64_t N, int64_t nnz);
+int kamd_gcn_lists_build(void* stream, int64_t M, int64_t N, int64_t nnz, const int64_t* indices, int64_t stride_d, int64_t stride_e,
+                         const void* values, int value_bytes, int64_t stride_v, void* workspace, size_t workspace_bytes,
+                         int32_t* row_offsets, int32_t* cols, void* row_vals, int32_t* col_offsets, int32_t* rows, void* col_vals,
+                         int32_t* host_bad);
+int kamd_gcn_aggregate_f32(void* stream, int64_t R, int64_t S, int64_t nnz, int64_t B, int64_t P, const int32_t* offsets,
+                           const int32_t* idx, const float* vals, const float* x, int64_t xs_b, int64_t xs_n, int64_t xs_p,
+                           const float* src_norm, int normalize, float* norm_out, const float* addend, int64_t as_b, int64_t as_n,
+                           int64_t as_p, float* out);
+int kamd_gcn_aggregate_f64(void* stream, int64_t R, int64_t S, int64_t nnz, int64_t B, int64_t P, const int32_t* offsets,
+                           const int32_t* idx, const double* vals, const double* x, int64_t xs_b, int64_t xs_n, int64_t xs_p,
+                           const double* src_norm, int normalize, double* norm_out, const double* addend, int64_t as_b, int64_t as_n,
+                           int64_t as_p, double* out);
+int kamd_gcn_row_sums_f32(void* stream, int64_t M, int64_t nnz, const int32_t* offsets, const float* vals, float* norm);
+int kamd_gcn_row_sums_f64(void* stream, int64_t M, int64_t nnz, const int32_t* offsets, const double* vals, double* norm);
+int kamd_gcn_scale_values_f32(void* stream, int64_t M, int64_t nnz, const int64_t* rows, int64_t stride_e, const float* values,
+                              int64_t stride_v, const float* norm, float* out);
+int kamd_gcn_scale_values_f64(void* stream, int64_t M, int64_t nnz, const int64_t* rows, int64_t stride_e, const double* values,
+                              int64_t stride_v, const double* norm, double* out);
+
+/* ------------------------------------------------------------------------- */
 /* ops.mesh face_areas / sample_points (csrc/sample_points.hip; the reference  */
 /* is pure torch, kaolin/ops/mesh/trianglemesh.py:30-311: these entry points   */
 /* exist only on our side).  faces: int64 with element strides.  Items:        */

@@ -2353,8 +2353,136 @@ def farthest_point_sampling_cuda(points, k, path=None):
     return out
 
 
+# ---- kaolin.ops.gcn on csrc/gcn.hip (no reference operator: the reference calls torch.sparse.mm on a transposed copy) ---------------
+def _gcn_extents(fn, M, N, nnz):
+    if not (M >= 1 and N >= 1 and nnz >= 1):
+        raise ValueError(f'{fn}: a ({M}, {N}) matrix of {nnz} entries: every extent must be at least 1')
+    if max(M, N, nnz) >= 2 ** 31 - 1:
+        raise ValueError(f'{fn}: a ({M}, {N}) matrix of {nnz} entries: the lists hold int32, every extent must stay below 2^31 - 1')
+
+
+def _gcn_lists(fn, offsets, idx, vals, R, dev, dtype):
+    nnz = idx.numel() if isinstance(idx, torch.Tensor) else 0
+    torch_check(isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int32 and offsets.device == dev and
+                offsets.is_contiguous() and tuple(offsets.shape) == (R + 1,), f'{fn}: offsets must be a contiguous int tensor of size ({R + 1},)')
+    torch_check(isinstance(idx, torch.Tensor) and idx.dtype == torch.int32 and idx.device == dev and idx.is_contiguous() and
+                idx.dim() == 1, f'{fn}: idx must be a contiguous int tensor of size (nnz,)')
+    torch_check(isinstance(vals, torch.Tensor) and vals.dtype == dtype and vals.device == dev and vals.is_contiguous() and
+                tuple(vals.shape) == (nnz,), f'{fn}: vals must be a contiguous {dtype} tensor of size ({nnz},)')
+    return nnz
+
+
+def gcn_lists_cuda(indices, values, num_rows, num_cols):
+    """indices (2, nnz) long and values (nnz) float / double of a sparse COO (M, N) matrix, any strides -> (row_offsets (M + 1),
+    cols (nnz), row_vals (nnz), col_offsets (N + 1), rows (nnz), col_vals (nnz)): the entries of every row, and of every column, in
+    COO order (a stable sort by row / by column; ascending column order for a coalesced tensor); int32 and the values' dtype.
+
+    ONE host read (the count of entries outside the matrix: ``ValueError``); the call synchronises the current stream and cannot be
+    captured in a graph.  ``ValueError`` before any launch when M, N or nnz is 0 or reaches 2^31 - 1."""
+    fn = 'gcn_lists_cuda'
+    torch_check(isinstance(indices, torch.Tensor) and indices.is_cuda and indices.dtype == torch.int64 and indices.dim() == 2 and
+                indices.size(0) == 2, f'{fn}: indices must be a long CUDA tensor of size (2, nnz)')
+    sfx = _lib.dtype_suffix(values.dtype, fn)
+    torch_check(values.device == indices.device and tuple(values.shape) == (indices.size(1),), f'{fn}: values must be of size (nnz,)')
+    indices, values = indices.detach(), values.detach()
+    M, N, nnz, dev = int(num_rows), int(num_cols), indices.size(1), indices.device
+    _gcn_extents(fn, M, N, nnz)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_gcn_lists_workspace(M, N, nnz)
+        ws = _lib.workspace(nbytes, dev)
+        row_offsets = torch.empty(M + 1, dtype=torch.int32, device=dev)
+        col_offsets = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        cols, rows = (torch.empty(nnz, dtype=torch.int32, device=dev) for _ in range(2))
+        row_vals, col_vals = (torch.empty(nnz, dtype=values.dtype, device=dev) for _ in range(2))
+        bad = ctypes.c_int32(0)
+        _lib.check(lib.kamd_gcn_lists_build(_lib.stream_ptr(dev), M, N, nnz, _lib.ptr(indices), indices.stride(0), indices.stride(1),
+                                            _lib.ptr(values), 4 if sfx == 'f32' else 8, values.stride(0), _lib.ptr(ws), nbytes,
+                                            _lib.ptr(row_offsets), _lib.ptr(cols), _lib.ptr(row_vals), _lib.ptr(col_offsets),
+                                            _lib.ptr(rows), _lib.ptr(col_vals), ctypes.cast(ctypes.pointer(bad), ctypes.c_void_p)), fn)
+    if bad.value != 0:                                                       # the one host read
+        raise ValueError(f'{fn}: {bad.value} of the {nnz} entries lie outside the ({M}, {N}) matrix')
+    return row_offsets, cols, row_vals, col_offsets, rows, col_vals
+
+
+def gcn_aggregate_cuda(offsets, idx, vals, dense, src_norm=None, normalize=False, addend=None):
+    """The lists of R rows (offsets (R + 1), idx (nnz), vals (nnz)) over the S source rows of dense (B, S, P) float / double of any
+    strides (0 included) -> (out (B, R, P), norm (R) or None): per element the sequential sum of ``vals * dense[b, idx, p]`` over the
+    row's entries in list order, one rounded multiply and one rounded add per entry; ``src_norm`` (S): every term reads
+    ``dense / src_norm[idx]``; ``normalize``: the sum is divided once by the row's sequential sum of values, which is returned;
+    ``addend`` (B, R, P) of any strides: added last.  One launch, no atomics, no host read: capturable, and two calls give the same
+    bits."""
+    fn = 'gcn_aggregate_cuda'
+    torch_check(isinstance(dense, torch.Tensor) and dense.is_cuda and dense.dim() == 3, f'{fn}: dense must be a CUDA tensor of size (B, S, P)')
+    sfx = _lib.dtype_suffix(dense.dtype, fn)
+    x = dense.detach()
+    (B, S, P), dev = x.shape, x.device
+    R = offsets.numel() - 1 if isinstance(offsets, torch.Tensor) else 0
+    nnz = _gcn_lists(fn, offsets, idx, vals, R, dev, x.dtype)
+    _gcn_extents(fn, R, S, nnz)
+    torch_check(B >= 1 and P >= 1, f'{fn}: dense of size {tuple(x.shape)}: every extent must be at least 1')
+    if src_norm is not None:
+        torch_check(src_norm.dtype == x.dtype and src_norm.device == dev and src_norm.is_contiguous() and
+                    tuple(src_norm.shape) == (S,), f'{fn}: src_norm must be a contiguous {x.dtype} tensor of size ({S},)')
+    a = None
+    if addend is not None:
+        torch_check(addend.dtype == x.dtype and addend.device == dev and tuple(addend.shape) == (B, R, P),
+                    f'{fn}: addend must be a {x.dtype} tensor of size {(B, R, P)}')
+        a = addend.detach()
+    a_strides = a.stride() if a is not None else (0, 0, 0)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.empty((B, R, P), dtype=x.dtype, device=dev)
+        norm = torch.empty(R, dtype=x.dtype, device=dev) if normalize else None
+        _lib.check(getattr(lib, f'kamd_gcn_aggregate_{sfx}')(
+            _lib.stream_ptr(dev), R, S, nnz, B, P, _lib.ptr(offsets), _lib.ptr(idx), _lib.ptr(vals), _lib.ptr(x), x.stride(0), x.stride(1),
+            x.stride(2), _lib.ptr(src_norm), 1 if normalize else 0, _lib.ptr(norm), _lib.ptr(a), *a_strides, _lib.ptr(out)), fn)
+    return out, norm
+
+
+def gcn_row_sums_cuda(offsets, vals):
+    """The row lists -> norm (M): per row the sequential sum of its values in list order.  One launch."""
+    fn = 'gcn_row_sums_cuda'
+    torch_check(isinstance(vals, torch.Tensor) and vals.is_cuda, f'{fn}: vals must be a CUDA tensor')
+    sfx = _lib.dtype_suffix(vals.dtype, fn)
+    M, nnz, dev = offsets.numel() - 1, vals.numel(), vals.device
+    torch_check(offsets.dtype == torch.int32 and offsets.device == dev and offsets.is_contiguous() and offsets.dim() == 1,
+                f'{fn}: offsets must be a contiguous int tensor of size (M + 1,)')
+    torch_check(vals.is_contiguous() and vals.dim() == 1, f'{fn}: vals must be a contiguous tensor of size (nnz,)')
+    _gcn_extents(fn, M, 1, nnz)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        norm = torch.empty(M, dtype=vals.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_gcn_row_sums_{sfx}')(_lib.stream_ptr(dev), M, nnz, _lib.ptr(offsets), _lib.ptr(vals),
+                                                           _lib.ptr(norm)), fn)
+    return norm
+
+
+def gcn_scale_values_cuda(indices, values, norm):
+    """indices (2, nnz) long, values (nnz) of any strides and norm (M) -> contiguous (nnz): ``values[e] / norm[indices[0, e]]`` in the
+    COO's own entry order.  One launch."""
+    fn = 'gcn_scale_values_cuda'
+    torch_check(isinstance(indices, torch.Tensor) and indices.is_cuda and indices.dtype == torch.int64 and indices.dim() == 2 and
+                indices.size(0) == 2, f'{fn}: indices must be a long CUDA tensor of size (2, nnz)')
+    sfx = _lib.dtype_suffix(values.dtype, fn)
+    indices, values = indices.detach(), values.detach()
+    nnz, M, dev = indices.size(1), norm.numel(), indices.device
+    torch_check(values.device == dev and tuple(values.shape) == (nnz,), f'{fn}: values must be of size (nnz,)')
+    torch_check(norm.dtype == values.dtype and norm.device == dev and norm.is_contiguous() and norm.dim() == 1,
+                f'{fn}: norm must be a contiguous {values.dtype} tensor of size (M,)')
+    _gcn_extents(fn, M, 1, nnz)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.empty(nnz, dtype=values.dtype, device=dev)
+        _lib.check(getattr(lib, f'kamd_gcn_scale_values_{sfx}')(_lib.stream_ptr(dev), M, nnz, _lib.ptr(indices), indices.stride(1),
+                                                               _lib.ptr(values), values.stride(0), _lib.ptr(norm), _lib.ptr(out)), fn)
+    return out
+
+
 # the reference groups these operators in sub-modules: kaolin._C.ops.mesh / kaolin._C.ops.conversions (bindings.cpp)
 import types as _types  # noqa: E402
+gcn = _types.SimpleNamespace(gcn_lists_cuda=gcn_lists_cuda, gcn_aggregate_cuda=gcn_aggregate_cuda,
+                             gcn_row_sums_cuda=gcn_row_sums_cuda, gcn_scale_values_cuda=gcn_scale_values_cuda)
 gaussians = _types.SimpleNamespace(transform_gaussians_forward_cuda=transform_gaussians_forward_cuda,
                                    transform_gaussians_backward_cuda=transform_gaussians_backward_cuda)
 mesh = _types.SimpleNamespace(unbatched_mesh_intersection_cuda=unbatched_mesh_intersection_cuda,

@@ -155,6 +155,14 @@ SIGNATURES.update({
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_vertex_gather_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] + [_i64] * 4 + [_vp, _vp, _i, _vp])
     SIGNATURES[f'kamd_vertex_gather_backward_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] + [_i64] * 3 + [_vp, _i, _i64, _i64, _vp, _i, _vp])
+SIGNATURES.update({
+    'kamd_gcn_lists_workspace': (_sz, [_i64, _i64, _i64]),
+    'kamd_gcn_lists_build': (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i, _i64, _vp, _sz] + [_vp] * 7),
+})
+for _t in ('f32', 'f64'):
+    SIGNATURES[f'kamd_gcn_aggregate_{_t}'] = (_i, [_vp] + [_i64] * 5 + [_vp] * 4 + [_i64] * 3 + [_vp, _i, _vp, _vp] + [_i64] * 3 + [_vp])
+    SIGNATURES[f'kamd_gcn_row_sums_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _vp, _vp])
+    SIGNATURES[f'kamd_gcn_scale_values_{_t}'] = (_i, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp])
 SIGNATURES['kamd_sample_cdf_workspace'] = (_sz, [_i64, _i64])
 for _t in ('f32', 'f64'):
     SIGNATURES[f'kamd_face_areas_{_t}'] = (_i, [_vp] + [_i64] * 3 + [_vp, _vp] + [_i64] * 3 + [_vp, _i64, _i64, _vp])
