@@ -1673,6 +1673,38 @@ size_t kamd_fps_workspace(int B, int N, int k, int path);
 int kamd_fps_f32(void* stream, int B, int N, int k, const float* points, int64_t* out, void* workspace, int path);
 
 /* ------------------------------------------------------------------------- */
+/* kaolin.physics (csrc/physics.hip; the reference runs NVIDIA Warp kernels,   */
+/* kaolin/physics/materials/neohookean_elastic_material.py, and reduces with   */
+/* a dense dFdz, physics/utils/torch_utilities.py: these entry points exist    */
+/* only on our side).  float32, contiguous.  No atomics: the same bits on      */
+/* every call.  No host read, no synchronisation: capturable.                  */
+/* neohookean: defo_grads (N, 3, 3), mu, lam, vol (N) -> energy (1), gradient  */
+/* (N, 3, 3), hessian (N, 9, 9), each scaled by vol * coeff; an output that is */
+/* NULL is not computed.  The cofactor comes from 2x2 minors: finite for a     */
+/* singular or inverted F.  workspace: kamd_physics_neohookean_workspace(N)    */
+/* bytes, needed for the energy only.  N == 0 launches nothing.                */
+/* reduced_neohookean: z (12 H) at index 12 h + 4 b + n, pts (N, 3), weights   */
+/* (N, H), weights_jac (N, H, 3) -> E (1), g (12 H), K (12 H, 12 H) of the     */
+/* Simplicits degrees of freedom, matrix-free (no dFdz, no per-point Hessian   */
+/* in memory).  hessian == 0: K is not computed and may be NULL.  1 <= H <=    */
+/* kamd_physics_max_handles() (the kernel's LDS image), N >= 1, else an error  */
+/* status.  The points are cut into slices of kamd_physics_slice_points(N, H)  */
+/* points, walked in chunks of kamd_physics_chunk_points(); workspace:         */
+/* kamd_physics_reduced_workspace(N, H, hessian) bytes, 16-byte aligned, not   */
+/* initialised.  All four queries are pure host arithmetic.                    */
+/* ------------------------------------------------------------------------- */
+size_t kamd_physics_neohookean_workspace(int64_t N);
+int kamd_physics_neohookean_f32(void* stream, int64_t N, const float* defo_grads, const float* mu, const float* lam, const float* vol,
+                                float coeff, float* energy, float* gradient, float* hessian, void* workspace);
+int kamd_physics_chunk_points(void);
+int kamd_physics_max_handles(void);
+int64_t kamd_physics_slice_points(int64_t N, int H);
+size_t kamd_physics_reduced_workspace(int64_t N, int H, int hessian);
+int kamd_physics_reduced_neohookean_f32(void* stream, int64_t N, int H, const float* z, const float* pts, const float* weights,
+                                        const float* weights_jac, const float* mu, const float* lam, const float* vol, float coeff,
+                                        int hessian, float* E, float* g, float* K, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

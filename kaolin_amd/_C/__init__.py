@@ -14,4 +14,4 @@ is done by hand-written HIP kernels in libkaolin_amd.so through the C ABI of
 include/kaolin_amd.h (the ``_cuda`` suffix is kept because callers spell it that
 way; on ROCm ``tensor.is_cuda`` is the HIP device).
 """
-from . import metrics, render, ops  # noqa: F401
+from . import metrics, render, ops, physics  # noqa: F401

@@ -1,0 +1,77 @@
+"""Host shims of csrc/physics.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
+Every argument is a contiguous float32 tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
+import torch
+
+from .. import _lib
+from .._checks import torch_check
+
+
+def _f32_cuda(fn, **tensors):
+    dev = None
+    for name, t in tensors.items():
+        torch_check(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(),
+                    f'{fn}: {name} must be a contiguous float CUDA tensor')
+        torch_check(dev is None or t.device == dev, f'{fn}: {name} is on another device')
+        dev = t.device
+    return dev
+
+
+def chunk_points():
+    """Points of one staging step of the reduced kernel"""
+    return int(_lib.load().kamd_physics_chunk_points())
+
+
+def slice_points(num_points, num_handles):
+    """Points of one slice (= one partial sum) of the reduced kernel at this size"""
+    return int(_lib.load().kamd_physics_slice_points(num_points, num_handles))
+
+
+def max_handles():
+    """The most handles the reduced kernel takes (its LDS image)"""
+    return int(_lib.load().kamd_physics_max_handles())
+
+
+def neohookean_cuda(defo_grads, mu, lam, vol, coeff, energy=True, gradient=True, hessian=True):
+    """defo_grads (N, 3, 3), mu, lam, vol (N) -> (energy (1), gradient (N, 3, 3), hessian (N, 9, 9)), each scaled by
+    vol * coeff; None where not asked for.  N == 0 returns zeros without a launch."""
+    fn = 'neohookean_cuda'
+    dev = _f32_cuda(fn, defo_grads=defo_grads, mu=mu, lam=lam, vol=vol)
+    N = defo_grads.size(0)
+    torch_check(tuple(defo_grads.shape) == (N, 3, 3) and mu.shape == lam.shape == vol.shape == (N,),
+                f'{fn}: defo_grads must be of size {{num_points, 3, 3}} and mu, lam, vol of size {{num_points}}')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        E = torch.zeros(1, dtype=torch.float32, device=dev) if energy else None
+        G = torch.empty((N, 3, 3), dtype=torch.float32, device=dev) if gradient else None
+        Hs = torch.empty((N, 9, 9), dtype=torch.float32, device=dev) if hessian else None
+        if N > 0:
+            ws = _lib.workspace(lib.kamd_physics_neohookean_workspace(N), dev) if energy else None
+            _lib.check(lib.kamd_physics_neohookean_f32(_lib.stream_ptr(dev), N, _lib.ptr(defo_grads), _lib.ptr(mu), _lib.ptr(lam),
+                                                       _lib.ptr(vol), float(coeff), _lib.ptr(E), _lib.ptr(G), _lib.ptr(Hs),
+                                                       _lib.ptr(ws)), fn)
+    return E, G, Hs
+
+
+def reduced_neohookean_cuda(z, pts, weights, weights_jac, mu, lam, vol, coeff, hessian=True):
+    """z (12 H), pts (N, 3), weights (N, H), weights_jac (N, H, 3), mu, lam, vol (N), N >= 1, H <= max_handles()
+    -> (E (1), g (12 H), K (12 H, 12 H) or None)"""
+    fn = 'reduced_neohookean_cuda'
+    dev = _f32_cuda(fn, z=z, pts=pts, weights=weights, weights_jac=weights_jac, mu=mu, lam=lam, vol=vol)
+    torch_check(weights.dim() == 2, f'{fn}: weights must be of size {{num_points, num_handles}}')
+    N, H = weights.shape
+    torch_check(N >= 1 and 1 <= H <= max_handles(), f'{fn}: needs a point and 1 to {max_handles()} handles')
+    torch_check(tuple(z.shape) == (12 * H,) and tuple(pts.shape) == (N, 3) and tuple(weights_jac.shape) == (N, H, 3) and
+                mu.shape == lam.shape == vol.shape == (N,), f'{fn}: sizes do not agree')
+    D = 12 * H
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        E = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty(D, dtype=torch.float32, device=dev)
+        K = torch.empty((D, D), dtype=torch.float32, device=dev) if hessian else None
+        nbytes = lib.kamd_physics_reduced_workspace(N, H, int(bool(hessian)))
+        ws = _lib.workspace(nbytes, dev)
+        _lib.check(lib.kamd_physics_reduced_neohookean_f32(
+            _lib.stream_ptr(dev), N, H, _lib.ptr(z), _lib.ptr(pts), _lib.ptr(weights), _lib.ptr(weights_jac), _lib.ptr(mu),
+            _lib.ptr(lam), _lib.ptr(vol), float(coeff), int(bool(hessian)), _lib.ptr(E), _lib.ptr(g), _lib.ptr(K), _lib.ptr(ws),
+            nbytes), fn)
+    return E, g, K

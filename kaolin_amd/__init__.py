@@ -28,6 +28,8 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
     kaolin_amd.render.lighting  spherical-gaussian (HIP reduced inner product) and spherical-harmonic shading
     kaolin_amd.render.spc       unbatched_raytrace (HIP depth-first octree walk), mark_pack_boundaries, diff, cumsum, cumprod,
                                 sum_reduce, prod_reduce, exponential_integration (HIP pack scans and reductions)
+    kaolin_amd.physics          materials.NeohookeanElasticMaterial, simplicits.reduced_neohookean_terms: energy, gradient and
+                                Hessian of the reduced degrees of freedom as one matrix-free MFMA kernel (HIP)
     kaolin_amd._C               the 8 operator bindings of ``kaolin._C`` on this path
     kaolin_amd.distributed      batch/view sharding over RCCL (new; the reference has none)
 
@@ -37,7 +39,7 @@ existing notebooks/tests written against the reference import it unchanged.
 import sys
 
 from . import _C  # noqa: F401
-from . import io, math, metrics, ops, render, rep, utils  # noqa: F401
+from . import io, math, metrics, ops, physics, render, rep, utils  # noqa: F401
 from . import distributed  # noqa: F401
 
 __version__ = '0.1.0'

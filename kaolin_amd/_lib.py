@@ -180,6 +180,15 @@ SIGNATURES.update({
     'kamd_fps_workspace': (_sz, [_i, _i, _i, _i]),
     'kamd_fps_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i]),
 })
+SIGNATURES.update({
+    'kamd_physics_neohookean_workspace': (_sz, [_i64]),
+    'kamd_physics_neohookean_f32': (_i, [_vp, _i64] + [_vp] * 4 + [_f] + [_vp] * 4),
+    'kamd_physics_chunk_points': (_i, []),
+    'kamd_physics_max_handles': (_i, []),
+    'kamd_physics_slice_points': (_i64, [_i64, _i]),
+    'kamd_physics_reduced_workspace': (_sz, [_i64, _i, _i]),
+    'kamd_physics_reduced_neohookean_f32': (_i, [_vp, _i64, _i] + [_vp] * 7 + [_f, _i] + [_vp] * 4 + [_sz]),
+})
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):
