@@ -1705,6 +1705,26 @@ int kamd_physics_reduced_neohookean_f32(void* stream, int64_t N, int H, const fl
                                         int hessian, float* E, float* g, float* K, void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------- */
+/* The Simplicits skinning network (csrc/skinning_mlp.hip; the reference runs  */
+/* kaolin/physics/simplicits/network.py in torch, the Jacobian by jacrev under */
+/* vmap).  Linear(3, width), ELU, (Linear(width, width), ELU) x num_layers,    */
+/* Linear(width, num_handles - 1) on (pts - bb_min) / (bb_max - bb_min), and a */
+/* constant handle: pts (N, 3), bb_min, bb_max (3), params = every Linear in   */
+/* order, row-major weight then bias, all float32 contiguous on the device ->  */
+/* weights (N, num_handles) with a last column of ones and weights_jac         */
+/* (N, num_handles, 3), d weights / d pts, with a last row of zeros: the       */
+/* layouts kamd_physics_reduced_neohookean_f32 reads.  One launch of at most   */
+/* kamd_physics_skinning_max_groups() workgroups striding over tiles of 64     */
+/* points; no workspace, no atomics, no host read: the same bits on every      */
+/* call, capturable.  width a multiple of 16 in [16, 128], num_layers >= 0,    */
+/* 2 <= num_handles <= kamd_physics_max_handles(), N >= 1, else an error       */
+/* status.                                                                     */
+/* ------------------------------------------------------------------------- */
+int kamd_physics_skinning_max_groups(void);
+int kamd_physics_skinning_mlp_f32(void* stream, int64_t N, int width, int num_layers, int num_handles, const float* pts,
+                                  const float* bb_min, const float* bb_max, const float* params, float* weights, float* weights_jac);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */
@@ -1729,6 +1749,10 @@ int kamd_triangle_distance_work_counters(int on, unsigned long long* out8);
 /* instructions, no LDS) applied to `n_matrices` matrices of 64 uint64 rows each: out[m][j] = column j of matrix m.  With       */
 /* reference != 0 the same through __shfl_xor, the form the fast one replaced.  tests/test_dibr_gpu.py checks both against numpy. */
 int kamd_debug_transpose64(void* stream, int n_matrices, const uint64_t* in, uint64_t* out, int reference);
+/* The two activation functions of csrc/skinning_mlp.hip alone, as that kernel evaluates them: elu[e] = y > 0 ? y : expm1f(y) and     */
+/* delu[e] = y > 0 ? 1 : expf(y) for n float32 values.  tools/time_skinning.py measures their ulp error with it: the constant of the */
+/* error bound in tests/test_skinning_gpu.py.                                                                                        */
+int kamd_debug_skinning_elu(void* stream, int64_t n, const float* y, float* elu, float* delu);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""Host shims of csrc/physics.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
+"""Host shims of csrc/physics.hip and csrc/skinning_mlp.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
 Every argument is a contiguous float32 tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
 import torch
 
@@ -75,3 +75,45 @@ def reduced_neohookean_cuda(z, pts, weights, weights_jac, mu, lam, vol, coeff, h
             _lib.ptr(lam), _lib.ptr(vol), float(coeff), int(bool(hessian)), _lib.ptr(E), _lib.ptr(g), _lib.ptr(K), _lib.ptr(ws),
             nbytes), fn)
     return E, g, K
+
+
+def skinning_max_groups():
+    """The most workgroups of one skinning_mlp_cuda launch; each strides over tiles of 64 points"""
+    return int(_lib.load().kamd_physics_skinning_max_groups())
+
+
+def skinning_mlp_cuda(pts, bb_min, bb_max, params, width, num_layers, num_handles):
+    """pts (N, 3), N >= 1, bb_min, bb_max (3), params: the Linear layers of Linear(3, width), ELU, (Linear(width, width), ELU) x
+    num_layers, Linear(width, num_handles - 1), as a list of (weight, bias) -> (weights (N, num_handles), weights_jac
+    (N, num_handles, 3)) with the constant handle, in one launch.  width a multiple of 16 in [16, 128], num_handles in
+    [2, max_handles()]."""
+    fn = 'skinning_mlp_cuda'
+    sizes = [(width, 3)] + [(width, width)] * num_layers + [(num_handles - 1, width)]
+    torch_check(len(params) == len(sizes) and all(tuple(w.shape) == s and tuple(b.shape) == s[:1] for (w, b), s in zip(params, sizes)),
+                f'{fn}: params must be (weight, bias) of sizes {sizes}')
+    packed = torch.cat([t.detach().reshape(-1) for wb in params for t in wb])
+    dev = _f32_cuda(fn, pts=pts, bb_min=bb_min, bb_max=bb_max, params=packed)
+    N = pts.size(0)
+    torch_check(tuple(pts.shape) == (N, 3) and N >= 1 and tuple(bb_min.shape) == tuple(bb_max.shape) == (3,),
+                f'{fn}: pts must be of size {{num_points >= 1, 3}} and bb_min, bb_max of size {{3}}')
+    torch_check(width % 16 == 0 and 16 <= width <= 128 and num_layers >= 0 and 2 <= num_handles <= max_handles(),
+                f'{fn}: needs a width in 16, 32 ... 128 and 2 to {max_handles()} handles')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        weights = torch.empty((N, num_handles), dtype=torch.float32, device=dev)
+        weights_jac = torch.empty((N, num_handles, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_physics_skinning_mlp_f32(_lib.stream_ptr(dev), N, width, num_layers, num_handles, _lib.ptr(pts),
+                                                     _lib.ptr(bb_min), _lib.ptr(bb_max), _lib.ptr(packed), _lib.ptr(weights),
+                                                     _lib.ptr(weights_jac)), fn)
+    return weights, weights_jac
+
+
+def skinning_elu_cuda(y):
+    """y (n) -> (elu(y), elu'(y)) as csrc/skinning_mlp.hip evaluates them (a measuring hook: tools/time_skinning.py)"""
+    fn = 'skinning_elu_cuda'
+    dev = _f32_cuda(fn, y=y)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        a, d = torch.empty_like(y), torch.empty_like(y)
+        _lib.check(lib.kamd_debug_skinning_elu(_lib.stream_ptr(dev), y.numel(), _lib.ptr(y), _lib.ptr(a), _lib.ptr(d)), fn)
+    return a, d

@@ -30,6 +30,8 @@ differentiable-rasterization and 3D-metrics hot path behind Kaolin's own Python 
                                 sum_reduce, prod_reduce, exponential_integration (HIP pack scans and reductions)
     kaolin_amd.physics          materials.NeohookeanElasticMaterial, simplicits.reduced_neohookean_terms: energy, gradient and
                                 Hessian of the reduced degrees of freedom as one matrix-free MFMA kernel (HIP)
+                                simplicits.SimplicitsMLP / SkinningModule: skinning weights and their Jacobian from one
+                                forward-mode pass, one MFMA launch with the activations in registers (HIP)
     kaolin_amd._C               the 8 operator bindings of ``kaolin._C`` on this path
     kaolin_amd.distributed      batch/view sharding over RCCL (new; the reference has none)
 

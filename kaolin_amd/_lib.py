@@ -188,6 +188,9 @@ SIGNATURES.update({
     'kamd_physics_slice_points': (_i64, [_i64, _i]),
     'kamd_physics_reduced_workspace': (_sz, [_i64, _i, _i]),
     'kamd_physics_reduced_neohookean_f32': (_i, [_vp, _i64, _i] + [_vp] * 7 + [_f, _i] + [_vp] * 4 + [_sz]),
+    'kamd_physics_skinning_max_groups': (_i, []),
+    'kamd_physics_skinning_mlp_f32': (_i, [_vp, _i64, _i, _i, _i] + [_vp] * 6),
+    'kamd_debug_skinning_elu': (_i, [_vp, _i64, _vp, _vp, _vp]),
 })
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
