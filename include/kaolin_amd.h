@@ -1725,6 +1725,61 @@ int kamd_physics_skinning_mlp_f32(void* stream, int64_t N, int width, int num_la
                                   const float* bb_min, const float* bb_max, const float* params, float* weights, float* weights_jac);
 
 /* ------------------------------------------------------------------------- */
+/* kaolin.physics.common.collisions (csrc/collisions.hip; the reference runs   */
+/* NVIDIA Warp kernels, kaolin/physics/common/collisions.py).  float32 and     */
+/* int32, contiguous.  No atomics: the same bits on every call.                */
+/* DETECTION in two calls around ONE host read (not capturable).  count: dx,   */
+/* x0 (N, 3), obj_ids, is_static (N), 1 <= N < 2^31, max_pairs >= 1 ->         */
+/* host_counts[0] = all contacts, host_counts[1] = the contacts that emit must */
+/* sort to keep the max_pairs smallest (a, b); the stream is synchronised.     */
+/* A pair a < b is a contact iff sqrt((ex ex + ey ey) + ez ez) <=              */
+/* detection_radius for e = (x0 + dx)_a - (x0 + dx)_b, one float32 rounding    */
+/* per operation, not both are static (is_static == 1), and not (same object   */
+/* and |x0_a - x0_b|^2 < immune_radius).  emit, with the same arguments, the   */
+/* same workspace untouched in between, emitted = host_counts[1] >= 1 and      */
+/* kept = min(host_counts[0], max_pairs): indices_a, indices_b (kept; -1 for a */
+/* static point), normals = e / d (zero for d == 0) and gaps = dot(e, n) n     */
+/* (kept, 3), sorted by (a, b), and pair_objects (kept, 2), the object ids of   */
+/* a and b, when not NULL.  Workspaces: kamd_collision_detect_workspace(N)     */
+/* and kamd_collision_emit_workspace(emitted) bytes, 16-byte aligned.          */
+/* TERMS of C contacts among N points, dx, dx0 (N, 3): energy (1), gradient    */
+/* (C, 3), hessian (C, 3, 3), each scaled by coeff, an output that is NULL is  */
+/* not computed, one launch per output and one more for the energy's sum;      */
+/* workspace: kamd_collision_terms_workspace(C) bytes, for the energy only.    */
+/* dt and nu arrive multiplied by the friction regularisation.  C == 0         */
+/* launches nothing.  An index outside [0, N) is a static side.                */
+/* REDUCED: weights (N, H), x0 (N, 3) -> E (1), g (12 H), K (12 H, 12 H) =     */
+/* J^T blockdiag(hessian) J for the collision Jacobian J = J_a - J_b, row      */
+/* 12 h + 4 b + n as in kamd_physics_reduced_neohookean_f32, matrix-free; no   */
+/* host read: capturable.  hessian == 0: K is not computed and may be NULL.    */
+/* C >= 1, 1 <= H <= kamd_physics_max_handles().  The contacts are cut into    */
+/* slices of kamd_collision_slice_contacts(C, H), walked in chunks of          */
+/* kamd_collision_chunk_contacts(); workspace:                                 */
+/* kamd_collision_reduced_workspace(C, H, hessian) bytes, not initialised.     */
+/* ------------------------------------------------------------------------- */
+size_t kamd_collision_detect_workspace(int64_t N);
+int kamd_collision_count_f32(void* stream, int64_t N, const float* dx, const float* x0, const int* obj_ids, const int* is_static,
+                             float detection_radius, float immune_radius, int64_t max_pairs, void* workspace, size_t workspace_bytes,
+                             int64_t* host_counts);
+size_t kamd_collision_emit_workspace(int64_t emitted);
+int kamd_collision_emit_f32(void* stream, int64_t N, const float* x0, const int* obj_ids, const int* is_static, float detection_radius,
+                            float immune_radius, int64_t max_pairs, void* workspace, size_t workspace_bytes, int64_t emitted,
+                            int64_t kept, void* emit_workspace, size_t emit_workspace_bytes, int* indices_a, int* indices_b,
+                            float* normals, float* gaps, int* pair_objects);
+size_t kamd_collision_terms_workspace(int64_t C);
+int kamd_collision_terms_f32(void* stream, int64_t C, int64_t N, const float* dx, const float* dx0, const float* gaps,
+                             const float* normals, const int* indices_a, const int* indices_b, float coeff, float radius,
+                             float barrier_ratio, float mu, float dt, float nu, float* energy, float* gradient, float* hessian,
+                             void* workspace);
+int kamd_collision_chunk_contacts(void);
+int64_t kamd_collision_slice_contacts(int64_t C, int H);
+size_t kamd_collision_reduced_workspace(int64_t C, int H, int hessian);
+int kamd_collision_reduced_f32(void* stream, int64_t C, int64_t N, int H, const float* dx, const float* dx0, const float* gaps,
+                               const float* normals, const int* indices_a, const int* indices_b, const float* weights,
+                               const float* x0, float coeff, float radius, float barrier_ratio, float mu, float dt, float nu,
+                               int hessian, float* E, float* g, float* K, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

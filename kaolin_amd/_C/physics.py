@@ -1,5 +1,7 @@
-"""Host shims of csrc/physics.hip and csrc/skinning_mlp.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
-Every argument is a contiguous float32 tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
+"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip and csrc/collisions.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
+Every argument is a contiguous float32 (indices: int32) tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
+import ctypes
+
 import torch
 
 from .. import _lib
@@ -117,3 +119,104 @@ def skinning_elu_cuda(y):
         a, d = torch.empty_like(y), torch.empty_like(y)
         _lib.check(lib.kamd_debug_skinning_elu(_lib.stream_ptr(dev), y.numel(), _lib.ptr(y), _lib.ptr(a), _lib.ptr(d)), fn)
     return a, d
+
+
+# ---- csrc/collisions.hip ----------------------------------------------------------------------------------------------------------------
+def _i32_cuda(fn, dev, **tensors):
+    for name, t in tensors.items():
+        torch_check(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.device == dev,
+                    f'{fn}: {name} must be a contiguous int CUDA tensor on the device of the others')
+
+
+def collision_chunk_contacts():
+    """Contacts of one staging step of the reduced collision kernel"""
+    return int(_lib.load().kamd_collision_chunk_contacts())
+
+
+def collision_slice_contacts(num_contacts, num_handles):
+    """Contacts of one slice (= one partial sum) of the reduced collision kernel at this size"""
+    return int(_lib.load().kamd_collision_slice_contacts(num_contacts, num_handles))
+
+
+def collision_detect_cuda(dx, x0, obj_ids, is_static, detection_radius, immune_radius, max_pairs):
+    """dx, x0 (N, 3), obj_ids, is_static (N) int32, N >= 1, max_pairs >= 1 -> (number of contacts found, indices_a, indices_b (C)
+    int32, normals, gaps (C, 3), pair_objects (C, 2) int32) for the C = min(found, max_pairs) smallest (a, b), sorted.  ONE host read: not capturable."""
+    fn = 'collision_detect_cuda'
+    dev = _f32_cuda(fn, dx=dx, x0=x0)
+    _i32_cuda(fn, dev, obj_ids=obj_ids, is_static=is_static)
+    N = x0.size(0)
+    torch_check(N >= 1 and tuple(dx.shape) == tuple(x0.shape) == (N, 3) and tuple(obj_ids.shape) == tuple(is_static.shape) == (N,) and
+                max_pairs >= 1, f'{fn}: needs dx, x0 of size {{num_points >= 1, 3}}, obj_ids, is_static of size {{num_points}}')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        nbytes = lib.kamd_collision_detect_workspace(N)
+        ws = _lib.workspace(nbytes, dev)
+        counts = (ctypes.c_int64 * 2)()
+        args = (_lib.ptr(x0), _lib.ptr(obj_ids), _lib.ptr(is_static), float(detection_radius), float(immune_radius), int(max_pairs),
+                _lib.ptr(ws), nbytes)
+        _lib.check(lib.kamd_collision_count_f32(_lib.stream_ptr(dev), N, _lib.ptr(dx), *args, counts), fn)
+        total, emitted = int(counts[0]), int(counts[1])
+        C = min(total, int(max_pairs))
+        ia = torch.empty(C, dtype=torch.int32, device=dev)
+        ib = torch.empty(C, dtype=torch.int32, device=dev)
+        normals = torch.empty((C, 3), dtype=torch.float32, device=dev)
+        gaps = torch.empty((C, 3), dtype=torch.float32, device=dev)
+        pair_objects = torch.empty((C, 2), dtype=torch.int32, device=dev)
+        if C > 0:
+            ebytes = lib.kamd_collision_emit_workspace(emitted)
+            es = _lib.workspace(ebytes, dev)
+            _lib.check(lib.kamd_collision_emit_f32(_lib.stream_ptr(dev), N, *args, emitted, C, _lib.ptr(es), ebytes, _lib.ptr(ia),
+                                                   _lib.ptr(ib), _lib.ptr(normals), _lib.ptr(gaps), _lib.ptr(pair_objects)), fn)
+    return total, ia, ib, normals, gaps, pair_objects
+
+
+def _contact_args(fn, dx, dx0, gaps, normals, indices_a, indices_b):
+    dev = _f32_cuda(fn, dx=dx, dx0=dx0, gaps=gaps, normals=normals)
+    _i32_cuda(fn, dev, indices_a=indices_a, indices_b=indices_b)
+    N, C = dx.size(0), indices_a.size(0)
+    torch_check(tuple(dx.shape) == tuple(dx0.shape) == (N, 3) and tuple(gaps.shape) == tuple(normals.shape) == (C, 3) and
+                tuple(indices_a.shape) == tuple(indices_b.shape) == (C,), f'{fn}: sizes do not agree')
+    return dev, N, C
+
+
+def collision_terms_cuda(dx, dx0, gaps, normals, indices_a, indices_b, coeff, radius, barrier_ratio, mu, dt, nu, which):
+    """The contact terms of C contacts among the N points of dx, dx0 (N, 3): `which` = 'energy' -> (1), 'gradient' -> (C, 3),
+    'hessian' -> (C, 3, 3), scaled by coeff.  C == 0 returns zeros without a launch."""
+    fn = 'collision_terms_cuda'
+    dev, N, C = _contact_args(fn, dx, dx0, gaps, normals, indices_a, indices_b)
+    shape = {'energy': (1,), 'gradient': (C, 3), 'hessian': (C, 3, 3)}[which]
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.zeros(shape, dtype=torch.float32, device=dev) if C == 0 else torch.empty(shape, dtype=torch.float32, device=dev)
+        if C > 0:
+            ws = _lib.workspace(lib.kamd_collision_terms_workspace(C), dev) if which == 'energy' else None
+            outs = [_lib.ptr(out) if which == name else None for name in ('energy', 'gradient', 'hessian')]
+            _lib.check(lib.kamd_collision_terms_f32(_lib.stream_ptr(dev), C, N, _lib.ptr(dx), _lib.ptr(dx0), _lib.ptr(gaps),
+                                                    _lib.ptr(normals), _lib.ptr(indices_a), _lib.ptr(indices_b), float(coeff),
+                                                    float(radius), float(barrier_ratio), float(mu), float(dt), float(nu), *outs,
+                                                    _lib.ptr(ws)), fn)
+    return out
+
+
+def collision_reduced_cuda(dx, dx0, gaps, normals, indices_a, indices_b, weights, x0, coeff, radius, barrier_ratio, mu, dt, nu,
+                           hessian=True):
+    """As collision_terms_cuda with weights (N, H), x0 (N, 3), C >= 1, H <= max_handles() -> (E (1), g (12 H), K (12 H, 12 H) or None)"""
+    fn = 'collision_reduced_cuda'
+    dev, N, C = _contact_args(fn, dx, dx0, gaps, normals, indices_a, indices_b)
+    torch_check(_f32_cuda(fn, weights=weights, x0=x0) == dev and weights.dim() == 2, f'{fn}: weights must be of size {{num_points, num_handles}}')
+    H = weights.size(1)
+    torch_check(C >= 1 and 1 <= H <= max_handles() and tuple(weights.shape) == (N, H) and tuple(x0.shape) == (N, 3),
+                f'{fn}: needs a contact, 1 to {max_handles()} handles and weights, x0 of {N} points')
+    D = 12 * H
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        E = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty(D, dtype=torch.float32, device=dev)
+        K = torch.empty((D, D), dtype=torch.float32, device=dev) if hessian else None
+        nbytes = lib.kamd_collision_reduced_workspace(C, H, int(bool(hessian)))
+        ws = _lib.workspace(nbytes, dev)
+        _lib.check(lib.kamd_collision_reduced_f32(
+            _lib.stream_ptr(dev), C, N, H, _lib.ptr(dx), _lib.ptr(dx0), _lib.ptr(gaps), _lib.ptr(normals), _lib.ptr(indices_a),
+            _lib.ptr(indices_b), _lib.ptr(weights), _lib.ptr(x0), float(coeff), float(radius), float(barrier_ratio), float(mu),
+            float(dt), float(nu), int(bool(hessian)), _lib.ptr(E), _lib.ptr(g), _lib.ptr(K), _lib.ptr(ws), nbytes), fn)
+    return E, g, K

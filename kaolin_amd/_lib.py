@@ -192,6 +192,18 @@ SIGNATURES.update({
     'kamd_physics_skinning_mlp_f32': (_i, [_vp, _i64, _i, _i, _i] + [_vp] * 6),
     'kamd_debug_skinning_elu': (_i, [_vp, _i64, _vp, _vp, _vp]),
 })
+SIGNATURES.update({
+    'kamd_collision_detect_workspace': (_sz, [_i64]),
+    'kamd_collision_count_f32': (_i, [_vp, _i64] + [_vp] * 4 + [_f, _f, _i64, _vp, _sz, ctypes.POINTER(_i64)]),
+    'kamd_collision_emit_workspace': (_sz, [_i64]),
+    'kamd_collision_emit_f32': (_i, [_vp, _i64] + [_vp] * 3 + [_f, _f, _i64, _vp, _sz, _i64, _i64, _vp, _sz] + [_vp] * 5),
+    'kamd_collision_terms_workspace': (_sz, [_i64]),
+    'kamd_collision_terms_f32': (_i, [_vp, _i64, _i64] + [_vp] * 6 + [_f] * 6 + [_vp] * 4),
+    'kamd_collision_chunk_contacts': (_i, []),
+    'kamd_collision_slice_contacts': (_i64, [_i64, _i]),
+    'kamd_collision_reduced_workspace': (_sz, [_i64, _i, _i]),
+    'kamd_collision_reduced_f32': (_i, [_vp, _i64, _i64, _i] + [_vp] * 8 + [_f] * 6 + [_i] + [_vp] * 4 + [_sz]),
+})
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
 for _t in ('f32', 'f64'):
