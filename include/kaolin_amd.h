@@ -1725,6 +1725,58 @@ int kamd_physics_skinning_mlp_f32(void* stream, int64_t N, int width, int num_la
                                   const float* bb_min, const float* bb_max, const float* params, float* weights, float* weights_jac);
 
 /* ------------------------------------------------------------------------- */
+/* Training the skinning network (csrc/skinning_mlp_backward.hip): the same    */
+/* network applied to pts as they are (no bounding box, no constant handle),   */
+/* width a multiple of 16 in [16, 64], other ranges as above.  forward_save:   */
+/* weights (N, num_handles - 1), weights_jac (N, num_handles - 1, 3), and the  */
+/* pre-activations of every activated layer in `stash`,                       */
+/* kamd_physics_skinning_stash_workspace(N, width, num_layers) bytes, not      */
+/* initialised.  backward: grad_weights, grad_weights_jac of those shapes ->   */
+/* grad_params, packed as params.  At most                                     */
+/* kamd_physics_skinning_train_max_groups() workgroups stride over tiles of    */
+/* 64 points, each writes a partial gradient image to `workspace`              */
+/* (kamd_physics_skinning_backward_workspace bytes, not initialised), a        */
+/* finishing launch sums them in order: no atomics, no host read, the same     */
+/* bits on every call.  The queries are pure host arithmetic (0: sizes out of  */
+/* range).                                                                     */
+/* ------------------------------------------------------------------------- */
+int kamd_physics_skinning_train_max_groups(void);
+size_t kamd_physics_skinning_stash_workspace(int64_t N, int width, int num_layers);
+size_t kamd_physics_skinning_backward_workspace(int64_t N, int width, int num_layers, int num_handles);
+int kamd_physics_skinning_forward_save_f32(void* stream, int64_t N, int width, int num_layers, int num_handles, const float* pts,
+                                           const float* params, float* weights, float* weights_jac, float* stash);
+int kamd_physics_skinning_backward_f32(void* stream, int64_t N, int width, int num_layers, int num_handles, const float* pts,
+                                       const float* params, const float* stash, const float* grad_weights,
+                                       const float* grad_weights_jac, float* grad_params, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------- */
+/* The Simplicits training losses (csrc/simplicits_loss.hip; the reference's   */
+/* kaolin/physics/simplicits/losses.py in torch).  weights (N, num_weights),   */
+/* weights_jac (N, num_weights, 3), pts (N, 3), transforms (B, num_weights, 3, */
+/* 4), mu, lam (N) -> le = scale_le sum_{p, b} [(1 - interp) Psi_lin(F_pb) +   */
+/* interp Psi_neo(F_pb)] with F_pb the closed-form deformation gradient, lo =  */
+/* scale_lo mean((W^T W - I)^2), each one float (summed in float64 and rounded  */
+/* once), and gram_minus_identity                                              */
+/* (num_weights, num_weights), which the backward reads.  backward: grad_le,   */
+/* grad_lo (one float each, on the device) -> grad_weights, grad_weights_jac.  */
+/* 1 <= num_weights <= kamd_physics_max_handles() - 1, N >= 1, B >= 0; B == 0  */
+/* computes lo alone and reads none of weights_jac, pts, transforms, mu, lam   */
+/* (they may be NULL).  workspace:                                             */
+/* kamd_physics_simplicits_loss_workspace(N, num_weights) bytes, not           */
+/* initialised (pure host arithmetic).  No atomics, no host read.              */
+/* ------------------------------------------------------------------------- */
+size_t kamd_physics_simplicits_loss_workspace(int64_t N, int num_weights);
+int kamd_physics_simplicits_loss_f32(void* stream, int64_t N, int B, int num_weights, const float* weights, const float* weights_jac,
+                                     const float* pts, const float* transforms, const float* mu, const float* lam, float interp,
+                                     double scale_le, double scale_lo, float* le, float* lo, float* gram_minus_identity, void* workspace,
+                                     size_t workspace_bytes);
+int kamd_physics_simplicits_loss_backward_f32(void* stream, int64_t N, int B, int num_weights, const float* weights,
+                                              const float* weights_jac, const float* pts, const float* transforms, const float* mu,
+                                              const float* lam, float interp, float scale_le, float scale_lo,
+                                              const float* gram_minus_identity, const float* grad_le, const float* grad_lo,
+                                              float* grad_weights, float* grad_weights_jac);
+
+/* ------------------------------------------------------------------------- */
 /* kaolin.physics.common.collisions (csrc/collisions.hip; the reference runs   */
 /* NVIDIA Warp kernels, kaolin/physics/common/collisions.py).  float32 and     */
 /* int32, contiguous.  No atomics: the same bits on every call.                */

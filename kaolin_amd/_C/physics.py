@@ -1,4 +1,4 @@
-"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip and csrc/collisions.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
+"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip, csrc/skinning_mlp_backward.hip, csrc/simplicits_loss.hip and csrc/collisions.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
 Every argument is a contiguous float32 (indices: int32) tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
 import ctypes
 
@@ -119,6 +119,109 @@ def skinning_elu_cuda(y):
         a, d = torch.empty_like(y), torch.empty_like(y)
         _lib.check(lib.kamd_debug_skinning_elu(_lib.stream_ptr(dev), y.numel(), _lib.ptr(y), _lib.ptr(a), _lib.ptr(d)), fn)
     return a, d
+
+
+# ---- csrc/skinning_mlp_backward.hip, csrc/simplicits_loss.hip: training --------------------------------------------------------------
+def skinning_train_max_groups():
+    """The most workgroups (= partial gradient images) of the training launches; each strides over tiles of 64 points"""
+    return int(_lib.load().kamd_physics_skinning_train_max_groups())
+
+
+def _train_sizes(fn, pts, packed, width, num_layers, num_handles):
+    dev = _f32_cuda(fn, pts=pts, params=packed)
+    N = pts.size(0)
+    torch_check(tuple(pts.shape) == (N, 3) and N >= 1, f'{fn}: pts must be of size {{num_points >= 1, 3}}')
+    torch_check(width % 16 == 0 and 16 <= width <= 64 and num_layers >= 0 and 2 <= num_handles <= max_handles(),
+                f'{fn}: needs a width in 16, 32, 48, 64 and 2 to {max_handles()} handles')
+    torch_check(packed.numel() == 4 * width + num_layers * (width * width + width) + (num_handles - 1) * (width + 1),
+                f'{fn}: params must be every Linear in order, weight then bias, flat')
+    return dev, N
+
+
+def skinning_mlp_forward_save_cuda(pts, packed, width, num_layers, num_handles):
+    """The network of skinning_mlp_cuda on pts (N, 3) as they are, without the constant handle; packed: its parameters, flat ->
+    (weights (N, num_handles - 1), weights_jac (N, num_handles - 1, 3), stash for skinning_mlp_backward_cuda).  width <= 64."""
+    fn = 'skinning_mlp_forward_save_cuda'
+    dev, N = _train_sizes(fn, pts, packed, width, num_layers, num_handles)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        weights = torch.empty((N, num_handles - 1), dtype=torch.float32, device=dev)
+        weights_jac = torch.empty((N, num_handles - 1, 3), dtype=torch.float32, device=dev)
+        stash = torch.empty(lib.kamd_physics_skinning_stash_workspace(N, width, num_layers) // 4, dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_physics_skinning_forward_save_f32(_lib.stream_ptr(dev), N, width, num_layers, num_handles, _lib.ptr(pts),
+                                                              _lib.ptr(packed), _lib.ptr(weights), _lib.ptr(weights_jac),
+                                                              _lib.ptr(stash)), fn)
+    return weights, weights_jac, stash
+
+
+def skinning_mlp_backward_cuda(pts, packed, stash, grad_weights, grad_weights_jac, width, num_layers, num_handles):
+    """The reverse pass of skinning_mlp_forward_save_cuda: gradients of its two outputs -> the gradient of `packed`, flat"""
+    fn = 'skinning_mlp_backward_cuda'
+    dev, N = _train_sizes(fn, pts, packed, width, num_layers, num_handles)
+    torch_check(_f32_cuda(fn, stash=stash, grad_weights=grad_weights, grad_weights_jac=grad_weights_jac) == dev,
+                f'{fn}: the gradients are on another device')
+    lib = _lib.load()
+    torch_check(tuple(grad_weights.shape) == (N, num_handles - 1) and tuple(grad_weights_jac.shape) == (N, num_handles - 1, 3) and
+                stash.numel() * 4 == lib.kamd_physics_skinning_stash_workspace(N, width, num_layers), f'{fn}: sizes do not agree')
+    with _lib.on_device(dev):
+        grad = torch.empty_like(packed)
+        nbytes = lib.kamd_physics_skinning_backward_workspace(N, width, num_layers, num_handles)
+        ws = _lib.workspace(nbytes, dev)
+        _lib.check(lib.kamd_physics_skinning_backward_f32(_lib.stream_ptr(dev), N, width, num_layers, num_handles, _lib.ptr(pts),
+                                                          _lib.ptr(packed), _lib.ptr(stash), _lib.ptr(grad_weights),
+                                                          _lib.ptr(grad_weights_jac), _lib.ptr(grad), _lib.ptr(ws), nbytes), fn)
+    return grad
+
+
+def _loss_sizes(fn, weights, weights_jac, pts, transforms, mu, lam):
+    """B == 0 (transforms None): the orthogonality loss alone, of `weights` alone"""
+    torch_check(weights.dim() == 2, f'{fn}: weights must be of size {{num_points, num_weights}}')
+    N, HP = weights.shape
+    torch_check(N >= 1 and 1 <= HP <= max_handles() - 1, f'{fn}: needs a point and 1 to {max_handles() - 1} weights')
+    if transforms is None:
+        return _f32_cuda(fn, weights=weights), N, 0, HP
+    dev = _f32_cuda(fn, weights=weights, weights_jac=weights_jac, pts=pts, transforms=transforms, mu=mu, lam=lam)
+    B = transforms.size(0)
+    torch_check(B >= 1 and tuple(transforms.shape) == (B, HP, 3, 4) and tuple(weights_jac.shape) == (N, HP, 3) and
+                tuple(pts.shape) == (N, 3) and mu.shape == lam.shape == (N,), f'{fn}: sizes do not agree')
+    return dev, N, B, HP
+
+
+def simplicits_loss_cuda(weights, weights_jac, pts, transforms, mu, lam, interp, scale_le, scale_lo):
+    """weights (N, H'), weights_jac (N, H', 3), pts (N, 3), transforms (B, H', 3, 4), mu, lam (N) -> (le (), lo (), G - I (H', H'))
+    of csrc/simplicits_loss.hip; transforms None: lo alone (le = 0), the other inputs unread"""
+    fn = 'simplicits_loss_cuda'
+    dev, N, B, HP = _loss_sizes(fn, weights, weights_jac, pts, transforms, mu, lam)
+    opt = [_lib.ptr(t) if B else None for t in (weights_jac, pts, transforms, mu, lam)]
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        le = torch.empty((), dtype=torch.float32, device=dev)
+        lo = torch.empty((), dtype=torch.float32, device=dev)
+        gmi = torch.empty((HP, HP), dtype=torch.float32, device=dev)
+        nbytes = lib.kamd_physics_simplicits_loss_workspace(N, HP)
+        ws = _lib.workspace(nbytes, dev)
+        _lib.check(lib.kamd_physics_simplicits_loss_f32(_lib.stream_ptr(dev), N, B, HP, _lib.ptr(weights), *opt, float(interp),
+                                                        float(scale_le), float(scale_lo), _lib.ptr(le), _lib.ptr(lo), _lib.ptr(gmi),
+                                                        _lib.ptr(ws), nbytes), fn)
+    return le, lo, gmi
+
+
+def simplicits_loss_backward_cuda(weights, weights_jac, pts, transforms, mu, lam, interp, scale_le, scale_lo, gmi, grad_le, grad_lo):
+    """The gradient of simplicits_loss_cuda: grad_le, grad_lo (one float each, on the device) -> (grad_weights, grad_weights_jac)"""
+    fn = 'simplicits_loss_backward_cuda'
+    dev, N, B, HP = _loss_sizes(fn, weights, weights_jac, pts, transforms, mu, lam)
+    torch_check(_f32_cuda(fn, gmi=gmi, grad_le=grad_le, grad_lo=grad_lo) == dev and tuple(gmi.shape) == (HP, HP) and
+                grad_le.numel() == grad_lo.numel() == 1, f'{fn}: needs G - I of size {{{HP}, {HP}}} and two scalar gradients')
+    opt = [_lib.ptr(t) if B else None for t in (weights_jac, pts, transforms, mu, lam)]
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        grad_w = torch.empty((N, HP), dtype=torch.float32, device=dev)
+        grad_j = torch.empty((N, HP, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_physics_simplicits_loss_backward_f32(_lib.stream_ptr(dev), N, B, HP, _lib.ptr(weights), *opt,
+                                                                 float(interp), float(scale_le), float(scale_lo), _lib.ptr(gmi),
+                                                                 _lib.ptr(grad_le), _lib.ptr(grad_lo), _lib.ptr(grad_w),
+                                                                 _lib.ptr(grad_j)), fn)
+    return grad_w, grad_j
 
 
 # ---- csrc/collisions.hip ----------------------------------------------------------------------------------------------------------------

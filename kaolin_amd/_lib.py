@@ -191,6 +191,14 @@ SIGNATURES.update({
     'kamd_physics_skinning_max_groups': (_i, []),
     'kamd_physics_skinning_mlp_f32': (_i, [_vp, _i64, _i, _i, _i] + [_vp] * 6),
     'kamd_debug_skinning_elu': (_i, [_vp, _i64, _vp, _vp, _vp]),
+    'kamd_physics_skinning_train_max_groups': (_i, []),
+    'kamd_physics_skinning_stash_workspace': (_sz, [_i64, _i, _i]),
+    'kamd_physics_skinning_backward_workspace': (_sz, [_i64, _i, _i, _i]),
+    'kamd_physics_skinning_forward_save_f32': (_i, [_vp, _i64, _i, _i, _i] + [_vp] * 5),
+    'kamd_physics_skinning_backward_f32': (_i, [_vp, _i64, _i, _i, _i] + [_vp] * 7 + [_sz]),
+    'kamd_physics_simplicits_loss_workspace': (_sz, [_i64, _i]),
+    'kamd_physics_simplicits_loss_f32': (_i, [_vp, _i64, _i, _i] + [_vp] * 6 + [_f, _dbl, _dbl] + [_vp] * 4 + [_sz]),
+    'kamd_physics_simplicits_loss_backward_f32': (_i, [_vp, _i64, _i, _i] + [_vp] * 6 + [_f] * 3 + [_vp] * 5),
 })
 SIGNATURES.update({
     'kamd_collision_detect_workspace': (_sz, [_i64]),

@@ -15,6 +15,20 @@ These are a solver's forward quantities: nothing here records an autograd graph.
 The inputs of those come from a skinning network: :class:`SkinningModule` and :class:`SimplicitsMLP` (the reference's
 kaolin/physics/simplicits/network.py; state dicts interchange) give ``weights`` and ``weights_jac`` of any points, both from one
 forward pass that carries the three tangents (csrc/skinning_mlp.hip on a GPU), and :func:`standard_lbs` skins points with them.
+
+Training such a network (the reference's kaolin/physics/simplicits/losses.py): :func:`loss_elastic`, :func:`loss_ortho` and
+:func:`compute_losses`, over :func:`training_losses`, the two losses of given ``weights`` and ``weights_jac`` as one differentiable
+function.  float32 on a GPU runs csrc/simplicits_loss.hip (losses and their gradient) and, for a :class:`SimplicitsMLP` of width
+at most 64, csrc/skinning_mlp_backward.hip (the network's forward that keeps its pre-activations, and its reverse pass); everything
+else runs the torch definitions in this file.  A training loop is Adam around :func:`compute_losses`::
+
+    model = SimplicitsMLP(3, 64, num_handles, 6).cuda()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    for step in range(num_steps):
+        opt.zero_grad()
+        le, lo = compute_losses(model, pts, yms, prs, rhos, step / num_steps, 10, appx_vol, 1000, 1e-1, 1e6)
+        (le + lo).backward()
+        opt.step()
 """
 import types
 
@@ -23,10 +37,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _C
-from .materials import _check_floating, _neohookean_terms, _on_hip
+from .materials import _check_floating, _cofactor, _neohookean_terms, _on_hip, to_lame
 
 __all__ = ['dFdz_matrix', 'get_defo_grad', 'reduced_neohookean_terms', 'SkinningModule', 'SimplicitsMLP', 'weight_function_lbs',
-           'standard_lbs']
+           'standard_lbs', 'training_losses', 'loss_ortho', 'loss_elastic', 'compute_losses']
 
 
 def _check_skinning(weights, weights_jac, pts, **per_point):
@@ -213,7 +227,9 @@ class SimplicitsMLP(SkinningModule):
     :math:`[16, 128]`, ``2 <= num_handles <= kaolin_amd._C.physics.max_handles()``, at least a point, and no gradient wanted
     (grad mode off, or neither ``pts`` nor a parameter requires grad), all three methods run one HIP launch
     (csrc/skinning_mlp.hip): activations stay in registers from layer to layer, no workspace, the same bits on every call.
-    No autograd in HIP: the kernel gives the forward quantities of a simulation; anything that wants a gradient takes torch.
+    These three methods have no autograd in HIP: the kernel gives the forward quantities of a simulation, and a call of theirs
+    that wants a gradient takes torch.  Training has its own path: :func:`loss_elastic` and :func:`compute_losses` evaluate the
+    network (``layer_width <= 64``, ``pts`` not requiring grad) and its reverse pass in csrc/skinning_mlp_backward.hip.
 
     Args:
         spatial_dimensions (int): 3, or 2 (torch only).
@@ -247,11 +263,25 @@ class SimplicitsMLP(SkinningModule):
                 2 <= H <= _C.physics.max_handles() and pts.shape[0] >= 1 and
                 not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
 
-    def _forward_mode(self, pts):
-        """The definition, in torch: values y (N, W) and tangents T (N, 3, W) through the stack"""
+    def _trains_hip(self, pts):
+        """csrc/skinning_mlp_backward.hip serves the training losses, with or without a gradient wanted"""
         lin = self._linears()
-        y = F.linear(self._offset_scale(pts), lin[0].weight, lin[0].bias)
-        T = (lin[0].weight / (self.bb_max - self.bb_min).to(pts.dtype)).T[None]
+        W, H = lin[0].out_features, lin[-1].out_features + 1
+        tensors = [pts] + [t for m in lin for t in (m.weight, m.bias)]
+        return (lin[0].in_features == 3 and _on_hip(*tensors) and len({t.device for t in tensors}) == 1 and
+                not torch._C._functorch.is_functorch_wrapped_tensor(pts) and W % 16 == 0 and 16 <= W <= 64 and
+                2 <= H <= _C.physics.max_handles() and pts.dim() == 2 and pts.shape[0] >= 1 and not pts.requires_grad)
+
+    def _forward_mode(self, pts, box=None):
+        """The definition, in torch: values y (N, W) and tangents T (N, 3, W) through the stack; box: (bb_min, bb_max) to
+        normalise with, the module's own by default"""
+        lin = self._linears()
+        if box is None:
+            xn, ext = self._offset_scale(pts), (self.bb_max - self.bb_min).to(pts.dtype)
+        else:
+            xn, ext = (pts - box[0]) / (box[1] - box[0]), box[1] - box[0]
+        y = F.linear(xn, lin[0].weight, lin[0].bias)
+        T = (lin[0].weight / ext).T[None]
         for m in lin[1:]:
             T = T * torch.exp(y.clamp(max=0))[:, None, :]      # elu'(y): 1 for y > 0, exp(y) otherwise
             y, T = F.linear(F.elu(y), m.weight, m.bias), T @ m.weight.T
@@ -295,3 +325,210 @@ def standard_lbs(x0, tfms, w_x0):
         (torch.Tensor): the transformed points, of shape :math:`(N, B, 1, 3)`.
     """
     return (x0[:, None] + torch.einsum('nh,bhij,nj->nbi', w_x0, tfms, _homogeneous(x0)))[:, :, None]
+
+
+class _SkinningMLPTraining(torch.autograd.Function):
+    """(weights (N, H - 1), weights_jac (N, H - 1, 3)) of a SimplicitsMLP on pts as they are, csrc/skinning_mlp_backward.hip"""
+
+    @staticmethod
+    def forward(ctx, pts, dims, *params):
+        packed = torch.cat([t.detach().reshape(-1) for t in params])
+        weights, weights_jac, stash = _C.physics.skinning_mlp_forward_save_cuda(pts, packed, *dims)
+        ctx.save_for_backward(pts, packed, stash)
+        ctx.dims, ctx.shapes = dims, [t.shape for t in params]
+        return weights, weights_jac
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_weights, grad_weights_jac):
+        pts, packed, stash = ctx.saved_tensors
+        flat = _C.physics.skinning_mlp_backward_cuda(pts, packed, stash, grad_weights.contiguous(), grad_weights_jac.contiguous(),
+                                                     *ctx.dims)
+        grads = [g.view(shape) for g, shape in zip(flat.split([shape.numel() for shape in ctx.shapes]), ctx.shapes)]
+        return (None, None, *grads)
+
+
+def _weights_and_jac(model, pts):
+    """(weights (N, H'), weights_jac (N, H', 3)) of ``model(pts)``: the learned handles of the points as they are"""
+    if isinstance(model, SimplicitsMLP):
+        lin = model._linears()
+        if model._trains_hip(pts):
+            return _SkinningMLPTraining.apply(pts.contiguous(), (lin[0].out_features, len(lin) - 2, lin[-1].out_features + 1),
+                                              *(t for m in lin for t in (m.weight, m.bias)))
+        weights, weights_jac = model._forward_mode(pts, box=(0.0, 1.0))
+        return weights[:, :-1], weights_jac[:, :-1]
+    return model(pts), torch.vmap(torch.func.jacrev(lambda x: model(x[None])[0]))(pts)
+
+
+def _losses_definition(weights, weights_jac, pts, transforms, mus, lams, interp_step, scale_le, scale_lo):
+    """The two training losses in torch; transforms None: the elastic one is zero"""
+    Hp = weights.shape[1]
+    if transforms is None:
+        le = weights.new_zeros(())
+    else:
+        eye = torch.eye(3, dtype=weights.dtype, device=weights.device)
+        defo = eye + torch.einsum('ph,bhij->pbij', weights, transforms[..., :3]) + \
+            torch.einsum('bhin,pn,phj->pbij', transforms, _homogeneous(pts), weights_jac)
+        mu, lam = mus[:, None], lams[:, None]
+        eps = (defo + defo.transpose(-1, -2)) / 2 - eye
+        lin = mu * (eps * eps).sum(dim=(-1, -2)) + lam / 2 * eps.diagonal(dim1=-2, dim2=-1).sum(dim=-1) ** 2
+        J = _cofactor(defo.reshape(-1, 3, 3))[1].reshape(defo.shape[:2])
+        neo = mu / 2 * ((defo * defo).sum(dim=(-1, -2)) - 3) + lam / 2 * (J - 1) ** 2 - mu * (J - 1)
+        le = scale_le * ((1 - interp_step) * lin + interp_step * neo).sum()
+    gram = weights.T @ weights
+    return le, scale_lo * ((gram - torch.eye(Hp, dtype=weights.dtype, device=weights.device)) ** 2).mean()
+
+
+class _TrainingLosses(torch.autograd.Function):
+    """(le, lo) of csrc/simplicits_loss.hip; differentiable in weights and weights_jac"""
+
+    @staticmethod
+    def forward(ctx, weights, weights_jac, pts, transforms, mus, lams, interp_step, scale_le, scale_lo):
+        args = (weights, weights_jac, pts, transforms, mus, lams)
+        args = tuple(t if t is None else t.detach().contiguous() for t in args) + (interp_step, scale_le, scale_lo)
+        le, lo, gmi = _C.physics.simplicits_loss_cuda(*args)
+        ctx.save_for_backward(gmi, *(t for t in args[:6] if t is not None))
+        ctx.alone, ctx.scalars = transforms is None, args[6:]
+        return le, lo
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_le, grad_lo):
+        gmi, weights, *rest = ctx.saved_tensors
+        rest = [None] * 5 if ctx.alone else rest
+        grad_w, grad_j = _C.physics.simplicits_loss_backward_cuda(weights, *rest, *ctx.scalars, gmi, grad_le.contiguous(),
+                                                                  grad_lo.contiguous())
+        return (grad_w, None if ctx.alone else grad_j) + (None,) * 7
+
+
+def _losses(weights, weights_jac, pts, transforms, mus, lams, interp_step, scale_le, scale_lo):
+    """Dispatch of the two losses; transforms None: the orthogonality loss alone"""
+    tensors = [weights] if transforms is None else [weights, weights_jac, pts, transforms, mus, lams]
+    if (_on_hip(*tensors) and len({t.device for t in tensors}) == 1 and weights.shape[0] >= 1 and
+            1 <= weights.shape[1] <= _C.physics.max_handles() - 1 and (transforms is None or transforms.shape[0] >= 1) and
+            not any(t.requires_grad for t in tensors[2:]) and
+            not any(torch._C._functorch.is_functorch_wrapped_tensor(t) for t in tensors)):
+        return _TrainingLosses.apply(weights, weights_jac, pts, transforms, mus, lams, float(interp_step), float(scale_le),
+                                     float(scale_lo))
+    return _losses_definition(weights, weights_jac, pts, transforms, mus, lams, interp_step, scale_le, scale_lo)
+
+
+def training_losses(weights, weights_jac, pts, transforms, mus, lams, interp_step, scale_le=1.0, scale_lo=1.0):
+    r"""The elastic and the orthogonality loss of Simplicits training as one function of the skinning weights:
+
+    .. math::
+        le = \text{scale_le} \sum_{p, b} \left[ (1 - s) \Psi_{lin}(F_{pb}) + s \Psi_{neo}(F_{pb}) \right], \quad
+        lo = \text{scale_lo} \operatorname{mean}\left( (W^T W - I)^2 \right)
+
+    with :math:`F_{pb} = I + \sum_h ( w_{ph} T_{bh}[:, :3] + (T_{bh} \tilde x_p) \otimes \nabla w_{ph} )`,
+    :math:`\Psi_{lin} = \mu \|\epsilon\|^2 + \tfrac{\lambda}{2} \operatorname{tr}(\epsilon)^2`,
+    :math:`\epsilon = (F + F^T) / 2 - I`, and :math:`\Psi_{neo}` the Neo-Hookean energy of
+    :mod:`kaolin_amd.physics.materials` (determinant from 2x2 minors: finite for an inverted :math:`F`).
+
+    float32 tensors on one GPU with at most ``kaolin_amd._C.physics.max_handles() - 1`` weights a point run
+    csrc/simplicits_loss.hip, forward and backward: differentiable in ``weights`` and ``weights_jac`` (once), sums in one fixed
+    order, the same bits on every call.  Everything else, and a gradient wanted in any other argument, runs torch.
+
+    Args:
+        weights (torch.Tensor): skinning weights, of shape :math:`(N, H')`.
+        weights_jac (torch.Tensor): their spatial gradients, of shape :math:`(N, H', 3)`.
+        pts (torch.Tensor): the points, of shape :math:`(N, 3)`.
+        transforms (torch.Tensor): sample transforms of the handles, of shape :math:`(B, H', 3, 4)`.
+        mus, lams (torch.Tensor): Lame coefficients per point, each of shape :math:`(N,)`.
+        interp_step (float): :math:`s`, from 0 (linear elasticity) to 1 (Neo-Hookean).
+        scale_le, scale_lo (float): scale the two losses.
+
+    Returns:
+        (torch.Tensor, torch.Tensor): ``le`` and ``lo``, scalars.
+    """
+    N, Hp = _check_skinning(weights, weights_jac, pts, mus=mus, lams=lams)
+    _check_floating(weights=weights, transforms=transforms)
+    if transforms.dim() != 4 or tuple(transforms.shape[1:]) != (Hp, 3, 4):
+        raise ValueError(f'transforms must be of shape (B, {Hp}, 3, 4), got {tuple(transforms.shape)}')
+    return _losses(weights, weights_jac, pts, transforms, mus, lams, interp_step, scale_le, scale_lo)
+
+
+def loss_ortho(weights):
+    r"""The orthogonality loss of skinning weights, :math:`\operatorname{mean}((W^T W - I)^2)`.
+
+    Args:
+        weights (torch.Tensor): of shape :math:`(N, H')`.
+
+    Returns:
+        (torch.Tensor): a scalar; differentiable in ``weights`` (csrc/simplicits_loss.hip for float32 on a GPU).
+    """
+    _check_floating(weights=weights)
+    if weights.dim() != 2:
+        raise ValueError(f'weights must be of shape (N, H), got {tuple(weights.shape)}')
+    return _losses(weights, None, None, None, None, None, 0.0, 0.0, 1.0)[1]
+
+
+def _materials(yms, prs, interp_step, interp_material):
+    mus, lams = to_lame(yms.reshape(-1), prs.reshape(-1))
+    if interp_material:
+        mus = (1 - interp_step) * mus.min() + interp_step * mus
+        lams = (1 - interp_step) * lams.min() + interp_step * lams
+    return mus, lams
+
+
+def loss_elastic(model, pts, yms, prs, rhos, transforms, appx_vol, interp_step, elasticity_type="neohookean", interp_material=False):
+    r"""The elastic loss of Simplicits training: the energy of the points skinned by ``model`` under sample transforms,
+    :math:`\tfrac{\text{appx_vol}}{N} \sum_{p, b} [(1 - s) \Psi_{lin}(F_{pb}) + s \Psi_{neo}(F_{pb})]` (see
+    :func:`training_losses`), ramping from linear to Neo-Hookean elasticity with ``interp_step``.
+
+    ``model`` is applied to ``pts`` as they are: ``model(pts)`` gives the :math:`H'` learned weights, without bounding-box
+    normalisation and without the constant handle, as in the reference's training.  One difference from the reference is
+    deliberate: there :math:`F` comes from central finite differences of :func:`weight_function_lbs` with step
+    :math:`\sqrt{10^{-7}}` in float32; here it is the closed form above with the model's own Jacobian.
+
+    A float32 :class:`SimplicitsMLP` on a GPU (``layer_width`` a multiple of 16 up to 64, ``pts`` not requiring grad) is evaluated
+    and differentiated by csrc/skinning_mlp_backward.hip; another :class:`SimplicitsMLP` by its torch forward mode, any other
+    :class:`SkinningModule` by ``jacrev`` under ``vmap``.  Differentiable in the model's parameters.
+
+    Args:
+        model (SkinningModule): the skinning module.
+        pts (torch.Tensor): sample points, of shape :math:`(N, 3)`.
+        yms, prs, rhos (torch.Tensor): Young's moduli, Poisson ratios and densities per point, of shape :math:`(N,)` or
+            :math:`(N, 1)`; ``rhos`` is not used.
+        transforms (torch.Tensor): sample transforms, of shape :math:`(B, H', 3, 4)`.
+        appx_vol (float): the object's volume.
+        interp_step (float): :math:`s` in :math:`[0, 1]`.
+        elasticity_type (str): ``"neohookean"``; anything else raises ``ValueError``.
+        interp_material (bool): blend :math:`\mu, \lambda` from their minima to their values with ``interp_step``.
+
+    Returns:
+        (torch.Tensor): a scalar.
+    """
+    if elasticity_type != "neohookean":
+        raise ValueError(f"Elasticity type {elasticity_type} not supported")
+    mus, lams = _materials(yms, prs, interp_step, interp_material)
+    weights, weights_jac = _weights_and_jac(model, pts)
+    return training_losses(weights, weights_jac, pts, transforms, mus, lams, interp_step, appx_vol / pts.shape[0], 0.0)[0]
+
+
+def compute_losses(skinning_mod, normalized_pts, yms, prs, rhos, en_interp, batch_size, appx_vol, num_samples, le_coeff, lo_coeff):
+    r"""One step of Simplicits training: draws ``num_samples`` points (``torch.randint`` on the points' device) and ``batch_size``
+    transforms (``0.1 * torch.randn(batch_size, H', 3, 4)``), as the reference does, and returns
+    ``(le_coeff * loss_elastic, lo_coeff * loss_ortho)`` of them.  The network is evaluated once and both losses come from one
+    call of :func:`training_losses`; see :func:`loss_elastic` for the one difference from the reference.
+
+    Args:
+        skinning_mod (SkinningModule): the skinning module.
+        normalized_pts (torch.Tensor): the points, of shape :math:`(M, 3)`.
+        yms, prs, rhos (torch.Tensor): Young's moduli, Poisson ratios and densities per point, of shape :math:`(M,)`.
+        en_interp (float): the interpolation between the energies at this step.
+        batch_size (int): number of sample transforms.
+        appx_vol (float): the object's volume.
+        num_samples (int): number of sample points.
+        le_coeff, lo_coeff (float): coefficients of the two losses.
+
+    Returns:
+        (torch.Tensor, torch.Tensor): the elastic and the orthogonality term, scalars.
+    """
+    sample_indices = torch.randint(low=0, high=normalized_pts.shape[0], size=(num_samples,), device=normalized_pts.device)
+    sample_pts = normalized_pts[sample_indices]
+    mus, lams = _materials(yms[sample_indices], prs[sample_indices], en_interp, False)
+    weights, weights_jac = _weights_and_jac(skinning_mod, sample_pts)
+    batch_transforms = 0.1 * torch.randn(batch_size, weights.shape[-1], 3, 4, dtype=normalized_pts.dtype).to(normalized_pts.device)
+    le, lo = training_losses(weights, weights_jac, sample_pts, batch_transforms, mus, lams, en_interp, appx_vol / num_samples, 1.0)
+    return le_coeff * le, lo_coeff * lo
