@@ -3,10 +3,12 @@ oracle, bit for bit, and of the contact terms against float64 autograd of the re
 (tests/collisions_bruteforce.py).  Every figure is printed before it is asserted (pytest -s)."""
 import functools
 
+import numpy as np
 import pytest
 import torch
 
 import collisions_bruteforce as bf
+from kaolin_amd import _C
 from kaolin_amd.physics import Collision, collisions
 
 # what each case must contain for its rule to bite
@@ -22,10 +24,79 @@ BITES = {
 }
 
 
+
+
+def kept(name, col):
+    """Of the kept contacts of a case without static points: (cells of a (C, 3), cells of b, d (C)), and floor(pos / S) of every point"""
+    dx, x0, *_ = bf.detection_case(name)
+    pos, (_, S) = x0 + dx, bf.radii()
+    a, b = col.collision_indices_a.cpu().numpy(), col.collision_indices_b.cpu().numpy()
+    e = pos[a] - pos[b]
+    return bf.cell(pos[a], S), bf.cell(pos[b], S), np.sqrt(bf._dot(e, e)), np.floor(pos / S)
+
+
+def straddle_bites(col, total):
+    ca, cb, d, _ = kept('straddle', col)
+    apart = ca != cb
+    print(f'straddle: {total} contacts, {apart.any(axis=1).sum()} across a face, {(d == bf.radii()[0]).sum()} at d == R')
+    return apart.any(axis=1).sum() >= 20 and apart.any(axis=0).all() and (d == bf.radii()[0]).sum() >= 5 and (apart.sum(axis=1) >= 2).any()
+
+
+def clamp_bites(name, col, total):
+    ca, cb, _, q = kept(name, col)
+    edge, end = (32767, 65535) if name == 'clamp_hi' else (-32768, 0)
+    print(f'{name}: {total} contacts, {(ca != cb).any(axis=1).sum()} between different cells')
+    return (q > edge).any(axis=0).all() and (q < edge).any(axis=0).all() and (np.concatenate([ca, cb]) == end).all(axis=1).any() and \
+        total >= 30 and (ca != cb).any(axis=1).sum() >= 15
+
+
+def huge_bites(col, total):
+    dx, x0, obj, static, _ = bf.detection_case('huge')
+    n = len(x0) - bf.HUGE
+    alone = bf.detect(dx[:n], x0[:n], obj[:n], static[:n], 0.05)
+    with np.errstate(over='ignore'):
+        assert not np.isfinite((x0 + dx)[n:, None] - (x0 + dx)[None, n:]).all() and np.isfinite(x0 + dx).all()
+    return total == alone[0] > 10 and np.array_equal(col.collision_indices_a.cpu().numpy(), alone[1]) and \
+        np.array_equal(col.collision_indices_b.cpu().numpy(), alone[2])
+
+
+BITES.update({
+    'straddle': straddle_bites,
+    'clamp_hi': functools.partial(clamp_bites, 'clamp_hi'),
+    'clamp_lo': functools.partial(clamp_bites, 'clamp_lo'),
+    'huge': huge_bites,
+    'n4097': lambda col, total: 2 * 4097 < total < bf.ROOM['n4097'],                      # three sort blocks of 2048 keys, five scan blocks of 1024
+    'n65537': lambda col, total: 65537 < total < bf.ROOM['n65537'] and col.collision_indices_b.max() >= 65536,
+})
+
+
 @pytest.mark.parametrize('name', bf.DETECTION_CASES)
 def test_detection(name, caplog):
     col, total = bf.check_detection(name, 'cpu', caplog)
     assert BITES.get(name, lambda *_: True)(col, total)
+
+
+@pytest.mark.parametrize('name', bf.EDGE_DETECTION_CASES)
+def test_detection_edges(name, caplog):
+    col, total = bf.check_detection(name, 'cpu', caplog, max_pairs=bf.ROOM.get(name, 10000))
+    assert BITES[name](col, total)
+
+
+@pytest.mark.parametrize('name', ['n257', 'nan', 'static', 'duplicates', 'n4097'])
+def test_sweep_oracle_is_the_all_pairs_oracle(name):
+    dx, x0, obj, static, kw = bf.detection_case(name)
+    for max_pairs in (bf.ROOM.get(name, 10000), 37):
+        want = bf.detect(dx, x0, obj, static, kw['collision_particle_radius'], max_pairs=max_pairs)
+        got = bf.detect_sweep(dx, x0, obj, static, kw['collision_particle_radius'], max_pairs=max_pairs, block=64)
+        assert want[0] == got[0] > 3 and all(np.array_equal(p, q, equal_nan=True) for p, q in zip(want[1:], got[1:]))
+
+
+@pytest.mark.parametrize('label', bf.MAX_PAIRS_EDGES)
+def test_detection_max_pairs_edges(label, caplog):
+    """check_detection asserts the first min(T, max_pairs) pairs of the oracle, and the warning exactly when T > max_pairs"""
+    max_pairs = bf.max_pairs_edge(label)
+    col, total = bf.check_detection('n257', 'cpu', caplog, max_pairs=max_pairs)
+    assert col.num_contacts == min(total, max_pairs)
 
 
 def test_detection_overflow_keeps_the_smallest_pairs(caplog):
@@ -86,3 +157,34 @@ def test_reduced_terms_cpu():
     assert K2 is None and torch.equal(E2, E) and torch.equal(g2, g)
     col.num_contacts, col.collision_indices_a = 0, col.collision_indices_a[:0]
     assert [t.abs().sum().item() for t in col.reduced_terms(dx, w, x0, bf.COEFF)] == [0, 0, 0]
+
+
+@pytest.mark.parametrize('H', [5, 33])
+def test_elementwise_bound_bites(H):
+    """The float32 definition is within the per-element bound of the reduction at the kernel's slicing; the float64 sums without
+    one chunk of 32 contacts, and with the blocks (b, b') = (0, 1) and (1, 2) of K swapped, are not"""
+    C = 129
+    col, dx, w, x0 = bf.collision_of(bf.synthetic(C, 40, H, seed=100 * H + C), torch.float32, 'cpu')
+    per = _C.physics.collision_slice_contacts(C, H)
+    G, Hs, ia, ib = col.gradient(dx, x0, bf.COEFF), col.hessian(dx, x0, bf.COEFF), col.collision_indices_a, col.collision_indices_b
+    _, g, K = col.reduced_terms(dx, w, x0, bf.COEFF)
+    bf.check_reduced_elementwise(f'definition H={H}', g, K, G, Hs, w, x0, ia, ib, per, -(-C // per))
+    g_ref, K_ref, T_g, T_K = bf.reduced_sums(G, Hs, w, x0, ia, ib)
+    keep = torch.ones(C, 1)
+    keep[32:64] = 0
+    g_cut, K_cut, _, _ = bf.reduced_sums(G * keep, Hs * keep[:, :, None], w, x0, ia, ib)
+    blocks = K_ref.reshape(H, 3, 4, H, 3, 4)                                      # H_c is symmetric up to rounding: not (1, 0) for (0, 1)
+    K_swap = blocks.clone()
+    K_swap[:, 0, :, :, 1], K_swap[:, 1, :, :, 2] = blocks[:, 1, :, :, 2], blocks[:, 0, :, :, 1]
+    shares = [bf.bound_share(x, ref, T, per, -(-C // per)) for x, ref, T in ((g_cut, g_ref, T_g), (K_cut, K_ref, T_K), (K_swap.reshape(12 * H, 12 * H), K_ref, T_K))]
+    print(f'H={H}: share of the bound without a chunk g {shares[0]:.1f} K {shares[1]:.1f}, with two blocks swapped K {shares[2]:.1f}')
+    assert min(shares) > 1
+
+
+def test_regime_edges_cpu():
+    d, d_hat, vtn = bf.regime_edges()
+    bf.check_regime_edges('torch float32', bf.edge_terms(d, torch.float32), d, d_hat, vtn)
+    col, dx = bf.edge_collision(d, torch.float32, 'cpu')                          # the same contacts through the Collision's own path
+    E, G, Hs = bf.edge_terms(d, torch.float32)
+    assert torch.equal(col.gradient(dx, None, bf.COEFF), G) and torch.equal(col.hessian(dx, None, bf.COEFF), Hs)
+    assert torch.equal(col.energy(dx, None, bf.COEFF), E.sum().reshape(1))

@@ -2,7 +2,9 @@
 bit; the contact terms against float64 autograd of the analytic energy; the reduced terms against the float64 definition
 through collision_J_dense.  The measure and the yardstick are those of tests/test_physics_gpu.py (collisions_bruteforce.check):
 e = max|X - X64| / max|X64|, e_hip <= 4 max(e_def, 2^-24) and e_def < 1e-4, where e_def is the float32 torch formulation (the
-vectorised terms, the dense J), not the code under test.  Every figure is printed before it is asserted (pytest -s)."""
+vectorised terms, the dense J), not the code under test.  That measure is taken over a whole tensor, where the entries of K that
+carry the 1 of (x0, 1) dominate; the reduction itself (tile decode, mirroring, slices) is bounded per element against float64 sums
+over the terms kernel's own output (check_reduced_elementwise).  Every figure is printed before it is asserted (pytest -s)."""
 import functools
 
 import pytest
@@ -20,6 +22,12 @@ H_EDGES = (1, 4, 5, 17)   # 4 H: under one MFMA block, exactly one, a ragged one
 SLICE = {H: _C.physics.collision_slice_contacts(CC, H) for H in H_EDGES}
 EDGES = [(C, H) for H in (5, 17) for C in (CC - 1, CC, CC + 1, SLICE[H] - 1, SLICE[H], SLICE[H] + 1)]
 EDGES += [(C, H) for H in (1, 4) for C in (CC + 1, SLICE[H] + 1)]
+# W = 64: exactly one tile; two full tiles a side, the first full off-diagonal tile; three tile rows, (2, 0), (2, 1), (2, 2) ragged at
+# four rows; three full rows; max_handles(), 36 tiles
+H_TILES = (16, 32, 33, 48, _C.physics.max_handles())
+SLICE.update({H: _C.physics.collision_slice_contacts(CC, H) for H in H_TILES})
+TILE_EDGES = [(SLICE[H] + 1, H) for H in H_TILES] + [(CC - 1, 33)]
+MANY_SLICES = [(128 * 128 + 1, 1), (128 * 128 + 1, 5)]   # a slice above the minimum and rounded to the chunk, about a hundred slices
 
 
 @pytest.mark.parametrize('name', bf.DETECTION_CASES)
@@ -28,6 +36,30 @@ def test_detection(name, caplog):
     assert BITES.get(name, lambda *_: True)(col, total)
     if name == 'static':
         assert col.object_pairs.tolist() == [[0, 0], [0, 1], [1, 0], [1, 1]]
+
+
+@pytest.mark.parametrize('name', bf.EDGE_DETECTION_CASES)
+def test_detection_edges(name, caplog):
+    col, total = bf.check_detection(name, 'cuda', caplog, max_pairs=bf.ROOM.get(name, 10000))
+    print(f'{name}: {total} contacts')
+    assert BITES[name](col, total)
+
+
+@pytest.mark.parametrize('max_pairs', [bf.ROOM['n65537'], 10000])
+def test_detection_n65537(max_pairs, caplog):
+    """17-bit indices in the emit keys, against the sweep oracle; with the default max_pairs more pairs are emitted than kept"""
+    col, total = bf.check_detection('n65537', 'cuda', caplog, max_pairs=max_pairs, oracle=bf.detect_sweep)
+    print(f'n65537: {total} contacts, {col.num_contacts} kept')
+    assert 10000 < total < bf.ROOM['n65537'] and col.num_contacts == min(total, max_pairs)
+    if max_pairs > total:
+        assert BITES['n65537'](col, total)
+
+
+@pytest.mark.parametrize('label', bf.MAX_PAIRS_EDGES)
+def test_detection_max_pairs_edges(label, caplog):
+    max_pairs = bf.max_pairs_edge(label)
+    col, total = bf.check_detection('n257', 'cuda', caplog, max_pairs=max_pairs)
+    assert col.num_contacts == min(total, max_pairs)
 
 
 def test_detection_overflow_keeps_the_smallest_pairs(caplog):
@@ -53,15 +85,54 @@ def test_terms():
     assert col.energy(dx, x0, bf.COEFF, energy=total) is total and torch.equal(total, 1 + E)
 
 
+def test_terms_past_one_grid():
+    """C = 1024 * 256 + 257 contacts, contact c a copy of contact c % 300 of test_terms: the grid-stride loop of the terms kernel"""
+    d, _ = contacts()
+    C = 1024 * 256 + 257
+    index = torch.arange(C) % 300
+    tiled = {k: v[index] if k in ('gaps', 'normals', 'ia', 'ib') else v for k, v in d.items()}
+    small, dx, _, x0 = bf.collision_of(d, torch.float32, 'cuda')
+    col, *_ = bf.collision_of(tiled, torch.float32, 'cuda')
+    ref, dx32, _, x032 = bf.collision_of(tiled, torch.float32, 'cpu')
+    E64 = bf.energy64(collisions._contact_offsets(d['dx'], d['dx0'], d['gaps'], d['ia'], d['ib']), d['normals'],
+                      torch.where(d['ib'] < 0, 1.0, 2.0).double() * bf.RADIUS)[index].sum().reshape(1)
+    E, G, Hs = col.energy(dx, x0, bf.COEFF), col.gradient(dx, x0, bf.COEFF), col.hessian(dx, x0, bf.COEFF)
+    assert G.shape == (C, 3) and Hs.shape == (C, 3, 3)
+    assert torch.equal(G, small.gradient(dx, x0, bf.COEFF)[index.cuda()]) and torch.equal(Hs, small.hessian(dx, x0, bf.COEFF)[index.cuda()])
+    bf.check(f'energy C={C}', E, ref.energy(dx32, x032, bf.COEFF), E64)
+    assert all(torch.equal(a, b) for a, b in zip((E, G, Hs), (col.energy(dx, x0, bf.COEFF), col.gradient(dx, x0, bf.COEFF), col.hessian(dx, x0, bf.COEFF))))
+
+
+def test_regime_edges():
+    """d_hat at 1 and at rp and one float32 step beside them, |vt| at 0 and at 1 and one step beside it: per contact against float64"""
+    d, d_hat, vtn = bf.regime_edges()
+    col, dx = bf.edge_collision(d, torch.float32, 'cuda')
+    singles = [bf.edge_collision(d, torch.float32, 'cuda', slice(c, c + 1))[0] for c in range(len(d_hat))]
+    E = torch.cat([one.energy(dx, None, bf.COEFF) for one in singles])
+    bf.check_regime_edges('hip', (E, col.gradient(dx, None, bf.COEFF), col.hessian(dx, None, bf.COEFF)), d, d_hat, vtn)
+
+
 @functools.lru_cache(maxsize=None)
-def case(C, H, static=False):
-    assert _C.physics.collision_slice_contacts(C, H) == SLICE[H]
+def contacts_of(C, H, static=False):
     d = bf.synthetic(C, 40, H, seed=100 * H + C, static=static)
     return bf.collision_of(d, torch.float64, 'cuda'), bf.collision_of(d, torch.float32, 'cuda')
 
 
-def check_reduced(C, H, static=False):
-    (col64, *args64), (col, dx, w, x0) = case(C, H, static)
+def case(C, H, static=False):
+    assert _C.physics.collision_slice_contacts(C, H) == SLICE[H]
+    return contacts_of(C, H, static)
+
+
+def check_reduced_elementwise(name, col, dx, w, x0, g, K, per, slices):
+    """The reduction alone (indexing, tiles, mirroring, slices): g and K against the float64 sums over the HIP terms kernel's own
+    gradient and Hessian, per element (collisions_bruteforce.bound_share).  It rests on cl_contact giving the same bits in the
+    reduced kernel as in the terms kernel"""
+    bf.check_reduced_elementwise(name, g, K, col.gradient(dx, x0, bf.COEFF), col.hessian(dx, x0, bf.COEFF), w, x0,
+                                 col.collision_indices_a, col.collision_indices_b, per, slices)
+
+
+def check_reduced(C, H, static=False, contacts=case):
+    (col64, *args64), (col, dx, w, x0) = contacts(C, H, static)
     ref = col64.reduced_terms(*args64, bf.COEFF)
     definition = col._reduced_dense(col._contact_tensors(dx), w, x0, bf.COEFF, True)
     hip = col.reduced_terms(dx, w, x0, bf.COEFF)
@@ -70,12 +141,48 @@ def check_reduced(C, H, static=False):
         bf.check(f'reduced {name} C={C} H={H}', h, x, r)
     K = hip[2].reshape(H, 3, 4, H, 3, 4)
     assert torch.equal(K, K.permute(3, 1, 5, 0, 4, 2))        # K[12h+4b+n, 12h'+4b'+n'] == K[12h'+4b+n', 12h+4b'+n]
+    per = _C.physics.collision_slice_contacts(C, H)
+    check_reduced_elementwise(f'reduced C={C} H={H}', col, dx, w, x0, hip[1], hip[2], per, -(-C // per))
     return col, dx, w, x0, hip
 
 
 @pytest.mark.parametrize('C,H', EDGES)
 def test_reduced_terms(C, H):
     check_reduced(C, H)
+
+
+@pytest.mark.parametrize('C,H', TILE_EDGES)
+def test_reduced_terms_tile_rows(C, H):
+    check_reduced(C, H)
+
+
+@pytest.mark.parametrize('C,H', MANY_SLICES)
+def test_reduced_terms_many_slices(C, H):
+    per = _C.physics.collision_slice_contacts(C, H)
+    assert per > 128 and per % CC == 0 and -(-C // per) > 90
+    check_reduced(C, H, contacts=contacts_of)
+
+
+def test_reduced_terms_without_hessian_three_tile_rows():
+    """hessian=False at H = 33: the grid is (slices, tile rows), not the triangle"""
+    col, dx, w, x0, (E, g, K) = check_reduced(SLICE[33] + 1, 33)
+    E2, g2, K2 = col.reduced_terms(dx, w, x0, bf.COEFF, hessian=False)
+    assert K2 is None and torch.equal(E2, E) and torch.equal(g2, g)
+
+
+def test_reduced_terms_fallback_above_max_handles():
+    """One handle above max_handles() the torch formulation runs: the same yardstick, its definition the CPU's float32 result;
+    per element its sums are single dot products over the 3 C rows of J"""
+    H = _C.physics.max_handles() + 1
+    C = SLICE[H - 1] + 1
+    (col64, *args64), (col, dx, w, x0) = contacts_of(C, H)
+    ref = col64.reduced_terms(*args64, bf.COEFF)
+    cpu, *args = bf.collision_of(bf.synthetic(C, 40, H, seed=100 * H + C), torch.float32, 'cpu')
+    got = col.reduced_terms(dx, w, x0, bf.COEFF)
+    assert got[2].shape == (12 * H, 12 * H) and got[2].is_cuda
+    for name, h, x, r in zip('EgK', got, cpu.reduced_terms(*args, bf.COEFF), ref):
+        bf.check(f'fallback {name} C={C} H={H}', h, x, r)
+    check_reduced_elementwise(f'fallback C={C} H={H}', col, dx, w, x0, got[1], got[2], 3 * C, 1)
 
 
 def test_reduced_terms_static_sides_forms_and_repeats():
