@@ -1832,6 +1832,47 @@ int kamd_collision_reduced_f32(void* stream, int64_t C, int64_t N, int H, const 
                                int hessian, float* E, float* g, float* K, void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------- */
+/* kaolin.physics.common.scene_forces and the inertia term of a Newton step    */
+/* (csrc/scene_forces.hip; the reference runs NVIDIA Warp kernels and stores   */
+/* B^T M B).  float32 and int32, contiguous.  No atomics: the same bits on     */
+/* every call; no host read: capturable.  A term whose first pointer is NULL   */
+/* is absent.  Gravity: rho, gvol (N), g; floor: fvol (N), height, axis 0..2,  */
+/* flip; active iff x[axis] < height (flip: >), strict.                        */
+/* TERMS of ONE class (exactly one of rho, fvol, pins_sorted is not NULL) on   */
+/* dx, x0 (N, 3): energy (1), gradient (N, 3), hessian (N, 3, 3), scaled by    */
+/* coeff; an output that is NULL is not computed.  The P >= 1 pins arrive      */
+/* sorted by point: pins_sorted (P) ascending, pins_order (P) their places in  */
+/* the list, pinned_x (P, 3) in list order; a point sums its pins (gather).    */
+/* workspace: kamd_scene_terms_workspace(N) bytes, for the energy only.        */
+/* REDUCED: z (12 H), x0 (N, 3), weights (N, H) -> E (1), g (12 H), K (12 H,   */
+/* 12 H) of all terms present, row 12 h + 4 b + n as in                        */
+/* kamd_physics_reduced_neohookean_f32; K couples no two axes b != b' (exact   */
+/* zeros) and is symmetric to the bit.  The rows are the N points, then the P  */
+/* pins: pinned_indices (P), pinned_x (P, 3), pinned_coeff (P); an index       */
+/* outside [0, N) reads nothing and adds nothing.  Inertia (mass (N) not NULL):*/
+/* delta = (z - z_prev) - dt z_dot, 1/2 mass |B_p delta|^2 per point, unscaled.*/
+/* hessian == 0: K is not computed and may be NULL.  N + P >= 1, 1 <= H <=     */
+/* kamd_physics_max_handles().  The rows are cut into slices of                */
+/* kamd_scene_slice_rows(N + P, H), walked in chunks of                        */
+/* kamd_scene_chunk_rows(); workspace: kamd_scene_reduced_workspace(N + P, H,  */
+/* hessian) bytes, not initialised.                                            */
+/* ------------------------------------------------------------------------- */
+size_t kamd_scene_terms_workspace(int64_t N);
+int kamd_scene_terms_f32(void* stream, int64_t N, const float* dx, const float* x0, const float* rho, const float* gvol, float gx,
+                         float gy, float gz, const float* fvol, float floor_height, int floor_axis, int flip_floor, int64_t P,
+                         const int* pins_sorted, const int* pins_order, const float* pinned_x, float coeff, float* energy,
+                         float* gradient, float* hessian, void* workspace);
+int kamd_scene_chunk_rows(void);
+int64_t kamd_scene_slice_rows(int64_t rows, int H);
+size_t kamd_scene_reduced_workspace(int64_t rows, int H, int hessian);
+int kamd_scene_reduced_f32(void* stream, int64_t N, int64_t P, int H, const float* z, const float* x0, const float* weights,
+                           const float* rho, const float* gvol, float gx, float gy, float gz, float gravity_coeff, const float* fvol,
+                           float floor_height, int floor_axis, int flip_floor, float floor_coeff, const int* pinned_indices,
+                           const float* pinned_x, const float* pinned_coeff, const float* mass, const float* z_prev,
+                           const float* z_dot, float dt, int hessian, float* E, float* g, float* K, void* workspace,
+                           size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -1,4 +1,4 @@
-"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip, csrc/skinning_mlp_backward.hip, csrc/simplicits_loss.hip and csrc/collisions.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
+"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip, csrc/skinning_mlp_backward.hip, csrc/simplicits_loss.hip, csrc/collisions.hip and csrc/scene_forces.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
 Every argument is a contiguous float32 (indices: int32) tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
 import ctypes
 
@@ -322,4 +322,94 @@ def collision_reduced_cuda(dx, dx0, gaps, normals, indices_a, indices_b, weights
             _lib.stream_ptr(dev), C, N, H, _lib.ptr(dx), _lib.ptr(dx0), _lib.ptr(gaps), _lib.ptr(normals), _lib.ptr(indices_a),
             _lib.ptr(indices_b), _lib.ptr(weights), _lib.ptr(x0), float(coeff), float(radius), float(barrier_ratio), float(mu),
             float(dt), float(nu), int(bool(hessian)), _lib.ptr(E), _lib.ptr(g), _lib.ptr(K), _lib.ptr(ws), nbytes), fn)
+    return E, g, K
+
+
+# ---- csrc/scene_forces.hip --------------------------------------------------------------------------------------------------------------
+def scene_chunk_rows():
+    """Rows (points, then pins) of one staging step of the reduced scene kernel"""
+    return int(_lib.load().kamd_scene_chunk_rows())
+
+
+def scene_slice_rows(num_rows, num_handles):
+    """Rows of one slice (= one partial sum) of the reduced scene kernel at this size"""
+    return int(_lib.load().kamd_scene_slice_rows(num_rows, num_handles))
+
+
+def _scene_class_args(fn, dev, N, gravity, floor):
+    """gravity (g (3 floats), rho (N), vol (N)) or None, floor (height, axis, flip, vol (N)) or None -> their C arguments, coefficients apart"""
+    g, rho, gvol = gravity if gravity is not None else ((0.0, 0.0, 0.0), None, None)
+    fh, axis, flip, fvol = floor if floor is not None else (0.0, 0, False, None)
+    per_point = {k: t for k, t in (('density', rho), ('gravity volume', gvol), ('floor volume', fvol)) if t is not None}
+    torch_check(all(_f32_cuda(fn, **{k: t}) == dev and tuple(t.shape) == (N,) for k, t in per_point.items()) and axis in (0, 1, 2),
+                f'{fn}: needs density and volume of size {{{N}}} on the device of the points and a floor axis in 0, 1, 2')
+    return ((_lib.ptr(rho), _lib.ptr(gvol), float(g[0]), float(g[1]), float(g[2])), (_lib.ptr(fvol), float(fh), int(axis), int(bool(flip))))
+
+
+def scene_terms_cuda(dx, x0, coeff, which, gravity=None, floor=None, pins=None):
+    """The terms of ONE class on dx, x0 (N, 3): gravity, floor as in _scene_class_args, pins (sorted (P) int32 ascending, order (P)
+    int32, pinned_x (P, 3)), P >= 1; `which` = 'energy' -> (1), 'gradient' -> (N, 3), 'hessian' -> (N, 3, 3), scaled by coeff.
+    N == 0 returns zeros without a launch."""
+    fn = 'scene_terms_cuda'
+    dev = _f32_cuda(fn, dx=dx, x0=x0)
+    N = x0.size(0)
+    torch_check(tuple(dx.shape) == tuple(x0.shape) == (N, 3) and (gravity is not None) + (floor is not None) + (pins is not None) == 1,
+                f'{fn}: needs dx, x0 of size {{num_points, 3}} and one class of terms')
+    gargs, fargs = _scene_class_args(fn, dev, N, gravity, floor)
+    P, pargs = 0, (None, None, None)
+    if pins is not None:
+        _i32_cuda(fn, dev, pins_sorted=pins[0], pins_order=pins[1])
+        P = pins[0].size(0)
+        torch_check(_f32_cuda(fn, pinned_x=pins[2]) == dev and P >= 1 and tuple(pins[1].shape) == (P,) and
+                    tuple(pins[2].shape) == (P, 3), f'{fn}: needs at least one pin and pinned_x of size {{num_pins, 3}}')
+        pargs = tuple(_lib.ptr(t) for t in pins)
+    shape = {'energy': (1,), 'gradient': (N, 3), 'hessian': (N, 3, 3)}[which]
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        out = torch.zeros(shape, dtype=torch.float32, device=dev) if N == 0 else torch.empty(shape, dtype=torch.float32, device=dev)
+        if N > 0:
+            ws = _lib.workspace(lib.kamd_scene_terms_workspace(N), dev) if which == 'energy' else None
+            outs = [_lib.ptr(out) if which == name else None for name in ('energy', 'gradient', 'hessian')]
+            _lib.check(lib.kamd_scene_terms_f32(_lib.stream_ptr(dev), N, _lib.ptr(dx), _lib.ptr(x0), *gargs, *fargs, P, *pargs,
+                                                float(coeff), *outs, _lib.ptr(ws)), fn)
+    return out
+
+
+def scene_reduced_cuda(z, x0, weights, gravity=None, gravity_coeff=0.0, floor=None, floor_coeff=0.0, pins=None, inertia=None,
+                       hessian=True):
+    """z (12 H), x0 (N, 3), weights (N, H), H <= max_handles(); gravity, floor as in _scene_class_args with their coefficients, pins
+    (indices (P) int32, pinned_x (P, 3), coefficients (P)), inertia (mass (N), z_prev (12 H), z_dot (12 H), dt); N + P >= 1
+    -> (E (1), g (12 H), K (12 H, 12 H) or None)"""
+    fn = 'scene_reduced_cuda'
+    dev = _f32_cuda(fn, z=z, x0=x0, weights=weights)
+    torch_check(weights.dim() == 2, f'{fn}: weights must be of size {{num_points, num_handles}}')
+    N, H = weights.shape
+    D = 12 * H
+    torch_check(1 <= H <= max_handles() and tuple(z.shape) == (D,) and tuple(x0.shape) == (N, 3),
+                f'{fn}: needs 1 to {max_handles()} handles, z of size {{12 num_handles}} and x0 of size {{num_points, 3}}')
+    gargs, fargs = _scene_class_args(fn, dev, N, gravity, floor)
+    P, pargs = 0, (None, None, None)
+    if pins is not None and pins[0].size(0) > 0:
+        _i32_cuda(fn, dev, pinned_indices=pins[0])
+        P = pins[0].size(0)
+        torch_check(_f32_cuda(fn, pinned_x=pins[1], pinned_coeff=pins[2]) == dev and tuple(pins[1].shape) == (P, 3) and
+                    tuple(pins[2].shape) == (P,), f'{fn}: needs pinned_x of size {{num_pins, 3}} and a coefficient per pin')
+        pargs = tuple(_lib.ptr(t) for t in pins)
+    iargs = (None, None, None, 0.0)
+    if inertia is not None:
+        mass, z_prev, z_dot, dt = inertia
+        torch_check(_f32_cuda(fn, mass=mass, z_prev=z_prev, z_dot=z_dot) == dev and tuple(mass.shape) == (N,) and
+                    tuple(z_prev.shape) == tuple(z_dot.shape) == (D,), f'{fn}: needs a mass per point and z_prev, z_dot of the size of z')
+        iargs = (_lib.ptr(mass), _lib.ptr(z_prev), _lib.ptr(z_dot), float(dt))
+    torch_check(N + P >= 1, f'{fn}: needs a point or a pin')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        E = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty(D, dtype=torch.float32, device=dev)
+        K = torch.empty((D, D), dtype=torch.float32, device=dev) if hessian else None
+        nbytes = lib.kamd_scene_reduced_workspace(N + P, H, int(bool(hessian)))
+        ws = _lib.workspace(nbytes, dev)
+        _lib.check(lib.kamd_scene_reduced_f32(
+            _lib.stream_ptr(dev), N, P, H, _lib.ptr(z), _lib.ptr(x0), _lib.ptr(weights), *gargs, float(gravity_coeff), *fargs,
+            float(floor_coeff), *pargs, *iargs, int(bool(hessian)), _lib.ptr(E), _lib.ptr(g), _lib.ptr(K), _lib.ptr(ws), nbytes), fn)
     return E, g, K

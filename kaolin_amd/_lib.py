@@ -211,6 +211,13 @@ SIGNATURES.update({
     'kamd_collision_slice_contacts': (_i64, [_i64, _i]),
     'kamd_collision_reduced_workspace': (_sz, [_i64, _i, _i]),
     'kamd_collision_reduced_f32': (_i, [_vp, _i64, _i64, _i] + [_vp] * 8 + [_f] * 6 + [_i] + [_vp] * 4 + [_sz]),
+    'kamd_scene_terms_workspace': (_sz, [_i64]),
+    'kamd_scene_terms_f32': (_i, [_vp, _i64] + [_vp] * 4 + [_f] * 3 + [_vp, _f, _i, _i, _i64] + [_vp] * 3 + [_f] + [_vp] * 4),
+    'kamd_scene_chunk_rows': (_i, []),
+    'kamd_scene_slice_rows': (_i64, [_i64, _i]),
+    'kamd_scene_reduced_workspace': (_sz, [_i64, _i, _i]),
+    'kamd_scene_reduced_f32': (_i, [_vp, _i64, _i64, _i] + [_vp] * 5 + [_f] * 4 + [_vp, _f, _i, _i, _f] + [_vp] * 6 + [_f, _i] +
+                               [_vp] * 4 + [_sz]),
 })
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])
