@@ -29,7 +29,7 @@
 //    (|vt| < 1e-4, < 1, >= 1) and the third-derivative chain term in the Hessian.  The Hessian is the derivative of the gradient,
 //    which the reference's is not in two places: its stick regime divides vt vt^T by |vt| dt where the derivative has |vt|, and
 //    its d3E takes d(barrier + dc / dp) as dbar - dc / dp^2 where it is dbar + (dp - dc) / dp^2.  cl_terms_kernel: one thread per contact,
-//    grid-stride, one launch per quantity; the energy adds up wave -> LDS -> one partial per workgroup -> cl_sum_kernel, in order.
+//    grid-stride, one launch per quantity; the energy adds up wave -> LDS -> one partial per workgroup -> ra_sum_kernel, in order.
 //
 // 3. cl_reduced_kernel: with W = 4 H, xt = (x0, 1) and  m_c[4 h + n] = w[a][h] xt_a[n] - w[b][h] xt_b[n]  (a static side: zeros),
 //    row 3 c + b of the collision Jacobian J = J_a - J_b holds m_c in the columns 12 h + 4 b + n, so
@@ -38,35 +38,26 @@
 //    and K[(h,b,n),(h',b',n')] = K_bb'[4 h + n][4 h' + n'].  H_c is not symmetric (the friction cross terms), so all nine (b, b')
 //    are computed; each K_bb' is symmetric in itself, so only the 64 x 64 tiles on and under the diagonal are, and of a diagonal
 //    tile only the 16 x 16 blocks on and under it.
-//    Grid (slice of contacts, tile), 256 threads.  The workgroup strides over its slice in chunks of CC = 32 contacts.  Per chunk:
+//    The grid, the sums of g and E, the slices' partials and their finish are those of reduced_assembly.h; the partials hold the nine
+//    blocks of RaFullNine.  The workgroup strides over its slice in chunks of CC = 32 contacts.  Per chunk:
 //      (a) thread q < 32 evaluates contact q: grad_c, H_c (and E) from the contact data -> LDS, with a, b and xt_a, xt_b
 //      (b) all threads gather the weight rows through a, b into the LDS images of m for the tile's rows and for its columns
 //          (zeros for a static side, past W and past the slice)
 //      (c) v_mfma_f32_16x16x4_f32: lane l holds A[row l & 15][k = l >> 4] = m_c[row] H_c[b][b'] and B[k][col l & 15] = m_c[col],
 //          c = 4 step + k: the scaling by H_c[b][b'] happens in the register (9 multiplies a step), no scaled image is written.
-//          Wavefront w owns rows 16 w .. 16 w + 15 and four 16-column blocks: 9 x 4 x 4 = 144 accumulator registers.
-//      g: the workgroups of column tile 0 (thread = (b, column): the chunk's contacts pairwise, chunks by a compensated sum);
-//      E: the workgroup of tile (0, 0).
-//    Each slice stores ONE partial; cl_finish_kernel adds the slices in index order and scatters to row 12 h + 4 b + n, reading
-//    entry (i, j) and (j, i) of a block from the same partials: K[12 h + 4 b + n][12 h' + 4 b' + n'] equals
-//    K[12 h' + 4 b + n'][12 h + 4 b' + n] to the bit.  No atomics, no host read: the same bits on every call, capturable.
+//          9 x 4 x 4 = 144 accumulator registers.
+//      g: grad_c[b] m_c of the row tile; E: in the threads that evaluate the contacts.
+//    The finish reads entry (i, j) and (j, i) of a block from the same partials: K[12 h + 4 b + n][12 h' + 4 b' + n'] equals
+//    K[12 h' + 4 b + n'][12 h + 4 b' + n] to the bit.
 //    LDS: 2 images of 32 x 80 floats (20 KiB) + 2.2 KiB of contact data.
+#include "reduced_assembly.h"
 #include "sort_scan.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
 
-typedef float cl_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CL_THREADS = 256;
-constexpr int CL_TERM_BLOCKS = 1024;           // most workgroups (= energy partials) of the per-contact kernel
 constexpr int CL_CC = 32;                      // contacts per chunk = GEMM depth of a chunk
-constexpr int CL_TILE = 64;
-constexpr int CL_LS = CL_TILE + 16;            // LDS row stride: lanes l and l + 16 read rows 80 dwords apart -> other banks
-constexpr int CL_MAX_H = 128;                  // = kamd_physics_max_handles()
-constexpr int CL_MIN_SLICE = 4 * CL_CC;
 constexpr int CL_MAX_SLICES = 128;
-constexpr int CL_TARGET_GROUPS = 512;          // slices x tiles aimed at: two workgroups per CU
 constexpr int CL_CELL_BITS = 16;
 constexpr int CL_CELL_MAX = (1 << CL_CELL_BITS) - 1;
 constexpr unsigned long long CL_NO_CELL = 1ull << (3 * CL_CELL_BITS);   // the key of a NaN or infinite point
@@ -159,18 +150,6 @@ __device__ __forceinline__ float cl_contact(const ClParams& p, const float* off,
   return p.coeff * E;
 }
 
-__device__ __forceinline__ float cl_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < KAMD_WAVE; m <<= 1) v = v + __shfl_xor(v, m);
-  return v;
-}
-// sum += v with the rounding error of every earlier step carried in `comp` (Kahan)
-__device__ __forceinline__ void cl_add(float& sum, float& comp, float v) {
-  const float y = v - comp, t = sum + y;
-  comp = (t - sum) - y;
-  sum = t;
-}
-
 struct ClContacts {
   int64_t C, N;
   const float *dx, *dx0, *gaps, *nor;
@@ -179,15 +158,14 @@ struct ClContacts {
 
 // MODE 0: energy partials, 1: gradient (C, 3), 2: Hessian (C, 3, 3)
 template <int MODE>
-__global__ __launch_bounds__(CL_THREADS) void cl_terms_kernel(const ClContacts k, const ClParams p, float* __restrict__ out) {
-  __shared__ float s_w[CL_THREADS / KAMD_WAVE];
+__global__ __launch_bounds__(RA_THREADS) void cl_terms_kernel(const ClContacts k, const ClParams p, float* __restrict__ out) {
   float e_acc = 0.0f, e_comp = 0.0f;
-  for (int64_t c = (int64_t)blockIdx.x * CL_THREADS + threadIdx.x; c < k.C; c += (int64_t)gridDim.x * CL_THREADS) {
+  for (int64_t c = (int64_t)blockIdx.x * RA_THREADS + threadIdx.x; c < k.C; c += (int64_t)gridDim.x * RA_THREADS) {
     float off[3], g[3], Hm[9];
     const float n[3] = {k.nor[c * 3], k.nor[c * 3 + 1], k.nor[c * 3 + 2]};
     const bool static_b = cl_offset(k.N, k.dx, k.dx0, k.gaps, k.ia[c], k.ib[c], c, off);
     const float e = cl_contact<MODE == 1, MODE == 2>(p, off, n, static_b, g, Hm);
-    if (MODE == 0) cl_add(e_acc, e_comp, e);
+    if (MODE == 0) ra_add(e_acc, e_comp, e);
     if (MODE == 1) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) out[c * 3 + j] = g[j];
@@ -197,19 +175,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_terms_kernel(const ClContacts k
       for (int j = 0; j < 9; ++j) out[c * 9 + j] = Hm[j];
     }
   }
-  if (MODE == 0) {
-    e_acc = cl_wave_sum(e_acc);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = e_acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-  }
-}
-// out[0] = the partials added in index order
-__global__ __launch_bounds__(KAMD_WAVE) void cl_sum_kernel(int n, const float* __restrict__ partial, float* __restrict__ out) {
-  if (threadIdx.x != 0) return;
-  float sum = 0.0f, comp = 0.0f;
-  for (int k = 0; k < n; ++k) cl_add(sum, comp, partial[k]);
-  out[0] = sum;
+  if (MODE == 0) ra_block_energy(e_acc, out);
 }
 
 // ---- 1. detection -------------------------------------------------------------------------------------------------------------------------
@@ -404,7 +370,7 @@ struct ClReduced {
   const float *w, *x0;   // (N, H), (N, 3)
   int64_t per;           // contacts per slice
   int H, W, T;           // handles, 4 H, tiles per side
-  float *Kp, *gp, *ep;   // partials (slice, 9, W, W), (slice, 3, W), (slice)
+  RaPartials part;       // K's blocks: (b, b')
 };
 
 // m_q[col] of the chunk's contact q (0 past W, for a static side and for a contact past the slice)
@@ -418,27 +384,23 @@ __device__ __forceinline__ float cl_m(const ClReduced& r, const int* s_a, const 
 }
 
 template <bool HESS>
-__global__ __launch_bounds__(CL_THREADS) void cl_reduced_kernel(const ClReduced r) {
-  __shared__ float s_MI[CL_CC * CL_LS], s_MJ[CL_CC * CL_LS];
+__global__ __launch_bounds__(RA_THREADS) void cl_reduced_kernel(const ClReduced r) {
+  __shared__ float s_MI[CL_CC * RA_LS], s_MJ[CL_CC * RA_LS];
   __shared__ float s_H[CL_CC * 9], s_g[CL_CC * 3], s_xa[CL_CC * 4], s_xb[CL_CC * 4], s_e[CL_CC];
   __shared__ int s_a[CL_CC], s_b[CL_CC];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t slice = blockIdx.x;
   int ti = (int)blockIdx.y, tj = 0;
-  if (HESS) {   // tile blockIdx.y of the lower triangle, row by row
-    ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.y) ++ti;
-    tj = (int)blockIdx.y - ti * (ti + 1) / 2;
-  }
-  const int i0 = ti * CL_TILE, j0 = tj * CL_TILE, W = r.W;
+  if (HESS) ra_lower_tile((int)blockIdx.y, ti, tj);
+  const int i0 = ti * RA_TILE, j0 = tj * RA_TILE, W = r.W;
   const bool diag = ti == tj, sums_g = tj == 0, sums_e = ti == 0 && tj == 0;
   const float* MJ = diag ? s_MI : s_MJ;
   const int64_t begin = slice * r.per, end = begin + r.per < r.k.C ? begin + r.per : r.k.C;
-  cl_f32x4 acc[9][4];
+  ra_f32x4 acc[9][4];
 #pragma unroll
   for (int pr = 0; pr < 9; ++pr)
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb) acc[pr][cb] = cl_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < 4; ++cb) acc[pr][cb] = ra_f32x4{0.f, 0.f, 0.f, 0.f};
   float g_acc = 0.0f, g_comp = 0.0f, e_acc = 0.0f, e_comp = 0.0f;
 
   for (int64_t c0 = begin; c0 < end; c0 += CL_CC) {
@@ -469,39 +431,35 @@ __global__ __launch_bounds__(CL_THREADS) void cl_reduced_kernel(const ClReduced 
 #pragma unroll
         for (int k = 0; k < 9; ++k) s_H[t * 9 + k] = Hm[k];
       }
-      if (sums_e) cl_add(e_acc, e_comp, e);
+      if (sums_e) ra_add(e_acc, e_comp, e);
     }
     __syncthreads();
     // (b) the images of m
-    for (int e = t; e < CL_CC * CL_TILE; e += CL_THREADS) {
+    for (int e = t; e < CL_CC * RA_TILE; e += RA_THREADS) {
       const int q = e >> 6, col = e & 63;
-      s_MI[q * CL_LS + col] = cl_m(r, s_a, s_b, s_xa, s_xb, q, i0 + col);
-      if (HESS && !diag) s_MJ[q * CL_LS + col] = cl_m(r, s_a, s_b, s_xa, s_xb, q, j0 + col);
+      s_MI[q * RA_LS + col] = cl_m(r, s_a, s_b, s_xa, s_xb, q, i0 + col);
+      if (HESS && !diag) s_MJ[q * RA_LS + col] = cl_m(r, s_a, s_b, s_xa, s_xb, q, j0 + col);
     }
     __syncthreads();
-    if (sums_g && t < 3 * CL_TILE) {
+    if (sums_g && t < 3 * RA_TILE) {
       const int b = t >> 6;  // per contact, then the chunk's contacts pairwise, then onto the running sum with its error carried
       float v[CL_CC];
 #pragma unroll
-      for (int q = 0; q < CL_CC; ++q) v[q] = s_g[q * 3 + b] * s_MI[q * CL_LS + lane];
-#pragma unroll
-      for (int w = 1; w < CL_CC; w <<= 1)
-#pragma unroll
-        for (int q = 0; q < CL_CC; q += 2 * w) v[q] = v[q] + v[q + w];
-      cl_add(g_acc, g_comp, v[0]);
+      for (int q = 0; q < CL_CC; ++q) v[q] = s_g[q * 3 + b] * s_MI[q * RA_LS + lane];
+      ra_add(g_acc, g_comp, ra_pairwise(v));
     }
     // (c) lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], D[row 4 (l >> 4) + reg][col l & 15]
     if (HESS && i0 + wave * 16 < W) {
       const int kq = lane >> 4, rr = lane & 15;
       for (int d = 0; d < CL_CC; d += 4) {
-        const float av = s_MI[(d + kq) * CL_LS + wave * 16 + rr];
+        const float av = s_MI[(d + kq) * RA_LS + wave * 16 + rr];
         float as[9];
 #pragma unroll
         for (int pr = 0; pr < 9; ++pr) as[pr] = av * s_H[(d + kq) * 9 + pr];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
           if (j0 + cb * 16 < W && (!diag || cb <= wave)) {
-            const float bv = MJ[(d + kq) * CL_LS + cb * 16 + rr];
+            const float bv = MJ[(d + kq) * RA_LS + cb * 16 + rr];
 #pragma unroll
             for (int pr = 0; pr < 9; ++pr) acc[pr][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(as[pr], bv, acc[pr][cb], 0, 0, 0);
           }
@@ -510,88 +468,13 @@ __global__ __launch_bounds__(CL_THREADS) void cl_reduced_kernel(const ClReduced 
   }
 
   if (HESS) {
-#pragma unroll
-    for (int pr = 0; pr < 9; ++pr) {
-      float* P = r.Kp + ((size_t)slice * 9 + pr) * (size_t)W * W;
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-        if (!diag || cb <= wave) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int row = i0 + wave * 16 + (lane >> 4) * 4 + j, col = j0 + cb * 16 + (lane & 15);
-            if (row < W && col < W) P[(size_t)row * W + col] = acc[pr][cb][j];
-          }
-        }
-    }
+    ra_store_blocks(acc, r.part.Kp, slice, W, i0, j0, wave, lane, diag);
   }
-  if (sums_g && t < 3 * CL_TILE && i0 + lane < W) r.gp[((size_t)slice * 3 + (t >> 6)) * W + i0 + lane] = g_acc;
-  if (sums_e) {
-    __syncthreads();
-    if (t < CL_CC) s_e[t] = e_acc;
-    __syncthreads();
-    if (t == 0) {
-      float sum = 0.0f, comp = 0.0f;
-      for (int q = 0; q < CL_CC; ++q) cl_add(sum, comp, s_e[q]);
-      r.ep[slice] = sum;
-    }
-  }
+  if (sums_g && t < 3 * RA_TILE && i0 + lane < W) r.part.gp[((size_t)slice * 3 + (t >> 6)) * W + i0 + lane] = g_acc;
+  if (sums_e) ra_slice_energy<CL_CC>(e_acc, t < CL_CC, t, s_e, r.part.ep + slice);
 }
 
-// the slices' partials added in index order -> K (D, D) (nullptr: none), g (D), E (1); D = 12 H, row = 12 h + 4 b + n
-__global__ __launch_bounds__(256) void cl_finish_kernel(int slices, int H, const float* __restrict__ Kp, const float* __restrict__ gp,
-                                                        const float* __restrict__ ep, float* __restrict__ K, float* __restrict__ g,
-                                                        float* __restrict__ E) {
-  const int64_t D = 12 * (int64_t)H, W = 4 * (int64_t)H;
-  const int64_t nK = K != nullptr ? D * D : 0, total = nK + D + 1;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const float* src;
-    int64_t step;
-    if (e < nK) {
-      const int64_t rw = e / D, c = e - rw * D;
-      const int b = (int)(rw % 12) / 4, bp = (int)(c % 12) / 4;
-      int64_t i = (rw / 12) * 4 + (rw & 3), j = (c / 12) * 4 + (c & 3);
-      if (i < j) {  // the mirrored entry of the same block
-        const int64_t si = i;
-        i = j, j = si;
-      }
-      src = Kp + ((size_t)(b * 3 + bp) * W + i) * W + j;
-      step = 9 * W * W;
-    } else if (e < nK + D) {
-      const int64_t rw = e - nK;
-      src = gp + ((rw % 12) / 4) * W + (rw / 12) * 4 + (rw & 3);
-      step = 3 * W;
-    } else {
-      src = ep;
-      step = 1;
-    }
-    float sum = src[0];
-    for (int s = 1; s < slices; ++s) sum = sum + src[(size_t)s * step];
-    if (e < nK)
-      K[e] = sum;
-    else if (e < nK + D)
-      g[e - nK] = sum;
-    else
-      E[0] = sum;
-  }
-}
-
-inline int cl_term_blocks(int64_t C) {
-  const int64_t blocks = (C + CL_THREADS - 1) / CL_THREADS;
-  return (int)(blocks < CL_TERM_BLOCKS ? blocks : CL_TERM_BLOCKS);
-}
-inline int cl_tiles(int H) { return (4 * H + CL_TILE - 1) / CL_TILE; }
-inline int cl_tri(int T) { return T * (T + 1) / 2; }
-inline int64_t cl_slice_contacts(int64_t C, int H) {
-  const int64_t tiles = cl_tri(cl_tiles(H));
-  int64_t slices = (CL_TARGET_GROUPS + tiles - 1) / tiles;
-  if (slices > CL_MAX_SLICES) slices = CL_MAX_SLICES;
-  const int64_t per = ((C + slices - 1) / slices + CL_CC - 1) / CL_CC * CL_CC;
-  return per < CL_MIN_SLICE ? CL_MIN_SLICE : per;
-}
-inline bool cl_sizes_ok(int64_t C, int64_t N, int H) {
-  return C >= 0 && C <= 0x7FFFFFFFLL && N >= 0 && N <= 0x7FFFFFFFLL && H >= 1 && H <= CL_MAX_H;
-}
-inline int64_t cl_slices(int64_t C, int H) { return (C + cl_slice_contacts(C, H) - 1) / cl_slice_contacts(C, H); }
+inline int64_t cl_slice_contacts(int64_t C, int H) { return ra_slice_len(C, ra_tri(ra_tiles(H)), CL_CC, CL_MAX_SLICES); }
 inline ClParams cl_params(float coeff, float radius, float rp, float mu, float dt, float nu) {
   ClParams p;
   p.coeff = coeff, p.radius = radius, p.rp = rp, p.mu = mu, p.dt = dt, p.nu = nu;
@@ -661,7 +544,7 @@ int kamd_collision_emit_f32(void* stream, int64_t N, const float* x0, const int*
   KAMD_RETURN_LAST_ERROR();
 }
 
-size_t kamd_collision_terms_workspace(int64_t C) { return C > 0 ? kamd_align16((size_t)cl_term_blocks(C) * sizeof(float)) : 0; }
+size_t kamd_collision_terms_workspace(int64_t C) { return C > 0 ? kamd_align16((size_t)ra_term_blocks(C, RA_THREADS) * sizeof(float)) : 0; }
 
 int kamd_collision_terms_f32(void* stream, int64_t C, int64_t N, const float* dx, const float* dx0, const float* gaps,
                              const float* normals, const int* indices_a, const int* indices_b, float coeff, float radius,
@@ -676,59 +559,44 @@ int kamd_collision_terms_f32(void* stream, int64_t C, int64_t N, const float* dx
   ClContacts k;
   k.C = C, k.N = N, k.dx = dx, k.dx0 = dx0, k.gaps = gaps, k.nor = normals, k.ia = indices_a, k.ib = indices_b;
   const ClParams p = cl_params(coeff, radius, barrier_ratio, mu, dt, nu);
-  const int blocks = cl_term_blocks(C);
+  const int blocks = ra_term_blocks(C, RA_THREADS);
   if (energy != nullptr) {
-    hipLaunchKernelGGL(cl_terms_kernel<0>, dim3((unsigned)blocks), dim3(CL_THREADS), 0, st, k, p, (float*)workspace);
-    hipLaunchKernelGGL(cl_sum_kernel, dim3(1), dim3(KAMD_WAVE), 0, st, blocks, (const float*)workspace, energy);
+    hipLaunchKernelGGL(cl_terms_kernel<0>, dim3((unsigned)blocks), dim3(RA_THREADS), 0, st, k, p, (float*)workspace);
+    hipLaunchKernelGGL(ra_sum_kernel, dim3(1), dim3(KAMD_WAVE), 0, st, blocks, (const float*)workspace, energy);
   }
-  if (gradient != nullptr) hipLaunchKernelGGL(cl_terms_kernel<1>, dim3((unsigned)blocks), dim3(CL_THREADS), 0, st, k, p, gradient);
-  if (hessian != nullptr) hipLaunchKernelGGL(cl_terms_kernel<2>, dim3((unsigned)blocks), dim3(CL_THREADS), 0, st, k, p, hessian);
+  if (gradient != nullptr) hipLaunchKernelGGL(cl_terms_kernel<1>, dim3((unsigned)blocks), dim3(RA_THREADS), 0, st, k, p, gradient);
+  if (hessian != nullptr) hipLaunchKernelGGL(cl_terms_kernel<2>, dim3((unsigned)blocks), dim3(RA_THREADS), 0, st, k, p, hessian);
   KAMD_RETURN_LAST_ERROR();
 }
 
 int kamd_collision_chunk_contacts(void) { return CL_CC; }
-int64_t kamd_collision_slice_contacts(int64_t C, int H) { return cl_sizes_ok(C, 0, H) ? cl_slice_contacts(C, H) : 0; }
+int64_t kamd_collision_slice_contacts(int64_t C, int H) { return ra_sizes_ok(C, H) ? cl_slice_contacts(C, H) : 0; }
 
 size_t kamd_collision_reduced_workspace(int64_t C, int H, int hessian) {
-  if (!cl_sizes_ok(C, 0, H) || C == 0) return 0;
-  const size_t S = (size_t)cl_slices(C, H), W = 4 * (size_t)H;
-  return (hessian ? kamd_align16(S * 9 * W * W * sizeof(float)) : 0) + kamd_align16(S * 3 * W * sizeof(float)) +
-         kamd_align16(S * sizeof(float));
+  if (!ra_sizes_ok(C, H) || C == 0) return 0;
+  return ra_workspace(ra_slices(C, cl_slice_contacts(C, H)), RaFullNine::BLOCKS, H, hessian);
 }
 
 int kamd_collision_reduced_f32(void* stream, int64_t C, int64_t N, int H, const float* dx, const float* dx0, const float* gaps,
                                const float* normals, const int* indices_a, const int* indices_b, const float* weights,
                                const float* x0, float coeff, float radius, float barrier_ratio, float mu, float dt, float nu,
                                int hessian, float* E, float* g, float* K, void* workspace, size_t workspace_bytes) {
-  if (!cl_sizes_ok(C, N, H) || C == 0) return (int)hipErrorInvalidValue;
+  if (!ra_sizes_ok(C, H) || N < 0 || N > 0x7FFFFFFFLL || C == 0) return (int)hipErrorInvalidValue;
   if (dx == nullptr || dx0 == nullptr || gaps == nullptr || normals == nullptr || indices_a == nullptr || indices_b == nullptr ||
       weights == nullptr || x0 == nullptr || E == nullptr || g == nullptr || (hessian && K == nullptr) || workspace == nullptr ||
       workspace_bytes < kamd_collision_reduced_workspace(C, H, hessian))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const size_t S = (size_t)cl_slices(C, H), W = 4 * (size_t)H;
-  char* ws = (char*)workspace;
   ClReduced r;
   r.k.C = C, r.k.N = N, r.k.dx = dx, r.k.dx0 = dx0, r.k.gaps = gaps, r.k.nor = normals, r.k.ia = indices_a, r.k.ib = indices_b;
   r.p = cl_params(coeff, radius, barrier_ratio, mu, dt, nu);
-  r.w = weights, r.x0 = x0, r.per = cl_slice_contacts(C, H), r.H = H, r.W = (int)W, r.T = cl_tiles(H);
-  r.Kp = nullptr;
-  if (hessian) {
-    r.Kp = (float*)ws;
-    ws += kamd_align16(S * 9 * W * W * sizeof(float));
-  }
-  r.gp = (float*)ws;
-  ws += kamd_align16(S * 3 * W * sizeof(float));
-  r.ep = (float*)ws;
+  r.w = weights, r.x0 = x0, r.per = cl_slice_contacts(C, H), r.H = H, r.W = 4 * H, r.T = ra_tiles(H);
+  const size_t S = ra_slices(C, r.per);
+  ra_workspace(S, RaFullNine::BLOCKS, H, hessian, workspace, &r.part);
   if (hessian)
-    hipLaunchKernelGGL(cl_reduced_kernel<true>, dim3((unsigned)S, (unsigned)cl_tri(r.T)), dim3(CL_THREADS), 0, st, r);
+    hipLaunchKernelGGL(cl_reduced_kernel<true>, dim3((unsigned)S, (unsigned)ra_tri(r.T)), dim3(RA_THREADS), 0, st, r);
   else
-    hipLaunchKernelGGL(cl_reduced_kernel<false>, dim3((unsigned)S, (unsigned)r.T), dim3(CL_THREADS), 0, st, r);
-  const int64_t D = 12 * (int64_t)H, total = (hessian ? D * D : 0) + D + 1;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > (int64_t)KAMD_NUM_CU * 16) blocks = (int64_t)KAMD_NUM_CU * 16;
-  hipLaunchKernelGGL(cl_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (int)S, H, (const float*)r.Kp, (const float*)r.gp,
-                     (const float*)r.ep, hessian ? K : (float*)nullptr, g, E);
-  KAMD_RETURN_LAST_ERROR();
+    hipLaunchKernelGGL(cl_reduced_kernel<false>, dim3((unsigned)S, (unsigned)r.T), dim3(RA_THREADS), 0, st, r);
+  return ra_finish<RaFullNine>(st, S, H, r.part, hessian ? K : nullptr, g, E);
 }
 }

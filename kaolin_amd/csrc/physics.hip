@@ -22,40 +22,27 @@
 //      K_bb'[i][j] = sum_p sum_m (Mcat_p[m][i] * sum_m' H_p[(b,m),(b',m')] Mcat_p[m'][j])     nine W x W GEMMs of depth 3 N
 //    and K[(h,b,n),(h',b',n')] = K_bb'[4 h + n][4 h' + n'].  K_b'b = K_bb'^T: the six pairs b' <= b are computed, and of the
 //    three b == b' only the tiles on and under the diagonal.
-//    Grid (slice of points, 64 x 64 tile of W x W), 256 threads.  The workgroup strides over its slice in chunks of PC = 16
-//    points (depth 48).  Per chunk:
+//    The grid, the sums of g and E, the slices' partials and their finish are those of reduced_assembly.h; the partials hold the
+//    six blocks of RaSymmetricSix.  The workgroup strides over its slice in chunks of PC = 16 points (depth 48).  Per chunk:
 //      (a) z is in LDS (12 H floats, staged once).  16 lanes per point accumulate F_p over the handles h = lane, lane + 16, ...
 //          and add up by a butterfly inside their row of 16; the first lane forms C, J, P (and Psi) and leaves F, C, P and
 //          (mu s, lam s, a s) in LDS
 //      (b) all threads build the two Mcat images in LDS, rows (point, m) x 64 columns of the row tile and of the column tile
 //          (zeros for columns past W and points past the slice), and the 81 entries of every H_p from F and C
 //      (c) for a pair (b, b'): R[(p, m)][j] = sum_m' H_p[(b,m),(b',m')] Mcat_p[m'][j] -> LDS
-//      (d) acc[pair] += McatI^T R by v_mfma_f32_16x16x4_f32: wavefront w owns rows 16 w ... 16 w + 15 of the tile and four
-//          16-column blocks; 6 pairs x 4 blocks x 4 = 96 accumulator registers.  Row and column blocks past W are skipped.
-//      g: the workgroups of column tile 0 add P_p Mcat_p for their row tile (thread = (b, column): the chunk's points pairwise,
-//         chunks by a compensated sum); E: the workgroup of tile (0, 0) adds Psi in the points' first lanes, compensated.
-//    Each slice stores ONE partial of K, g and E; ph_finish_kernel adds the slices in index order, mirrors (the entry (r, c)
-//    and the entry (c, r) read the same partials: K is symmetric to the bit) and scatters into the (12 H, 12 H) layout.
+//      (d) acc[pair] += McatI^T R: 6 pairs x 4 blocks x 4 = 96 accumulator registers.  Row and column blocks past W are skipped.
+//      g: P_p Mcat_p of the row tile; E: Psi, in the points' first lanes.
 //    LDS: 3 images of 48 x 80 floats (45 KiB) + H_p 5 KiB + F, C, P, x 2.2 KiB + z 48 H bytes: H <= 128 keeps it under 64 KiB.
-#include "common.h"
+#include "reduced_assembly.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
 
-typedef float ph_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int PH_PT_BLOCKS = 1024;             // most workgroups (= energy partials) of the point kernel
-constexpr int PH_THREADS = 256;
 constexpr int PH_PC = 16;                      // points per chunk
-constexpr int PH_TPP = PH_THREADS / PH_PC;     // lanes per point in stage (a)
+constexpr int PH_TPP = RA_THREADS / PH_PC;     // lanes per point in stage (a)
 constexpr int PH_DEPTH = 3 * PH_PC;            // GEMM depth of a chunk
-constexpr int PH_TILE = 64;
-constexpr int PH_LS = PH_TILE + 16;            // LDS row stride: lanes l and l + 16 read rows 80 dwords apart -> other banks
-constexpr int PH_MAX_H = 128;
-constexpr int PH_MIN_SLICE = 4 * PH_PC;
 constexpr int PH_MAX_SLICES = 64;
-constexpr int PH_TARGET_GROUPS = 512;          // slices x tiles aimed at: two workgroups per CU
-constexpr int PH_PAIRS = 6;
+constexpr int PH_PAIRS = RaSymmetricSix::BLOCKS;
 __device__ constexpr int PH_B[PH_PAIRS] = {0, 1, 1, 2, 2, 2}, PH_BP[PH_PAIRS] = {0, 0, 1, 0, 1, 2};
 
 // C = cof F: its rows are the cross products of F's other two rows; returns J = det F
@@ -95,17 +82,6 @@ __device__ __forceinline__ float ph_hess_entry(const float* F, const float* C, f
   }
   return v;
 }
-// sum += v with the rounding error of every earlier step carried in `comp` (Kahan; nothing here may be reassociated)
-__device__ __forceinline__ void ph_add(float& sum, float& comp, float v) {
-  const float y = v - comp, t = sum + y;
-  comp = (t - sum) - y;
-  sum = t;
-}
-__device__ __forceinline__ float ph_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < KAMD_WAVE; m <<= 1) v = v + __shfl_xor(v, m);
-  return v;
-}
 
 // ---- 1. the material on given F ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(KAMD_WAVE) void ph_material_kernel(int64_t N, const float* __restrict__ Fs, const float* __restrict__ mus,
@@ -129,7 +105,7 @@ __global__ __launch_bounds__(KAMD_WAVE) void ph_material_kernel(int64_t N, const
     }
     const float J = ph_cofactor(F, C);
     const float a = fmaf(lam, J - 1.0f, -mu);
-    if (partial != nullptr) ph_add(e_acc, e_comp, ph_energy(F, J, mu, lam));
+    if (partial != nullptr) ra_add(e_acc, e_comp, ph_energy(F, J, mu, lam));
     if (grad != nullptr) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) s_out[lane * 9 + k] = fmaf(mu, F[k], a * C[k]);
@@ -148,16 +124,9 @@ __global__ __launch_bounds__(KAMD_WAVE) void ph_material_kernel(int64_t N, const
     }
   }
   if (partial != nullptr) {
-    e_acc = ph_wave_sum(e_acc);
+    e_acc = ra_wave_sum(e_acc);
     if (lane == 0) partial[blockIdx.x] = e_acc;
   }
-}
-// out[0] = the partials added in index order
-__global__ __launch_bounds__(KAMD_WAVE) void ph_sum_kernel(int n, const float* __restrict__ partial, float* __restrict__ out) {
-  if (threadIdx.x != 0) return;
-  float sum = 0.0f, comp = 0.0f;
-  for (int k = 0; k < n; ++k) ph_add(sum, comp, partial[k]);
-  out[0] = sum;
 }
 
 // ---- 2. the reduced terms ---------------------------------------------------------------------------------------------------------------
@@ -166,7 +135,7 @@ struct PhArgs {
   float coeff;
   int64_t N, per;   // points, points per slice
   int H, W, T;      // handles, 4 H, tiles per side
-  float *Kp, *gp, *ep;  // partials (slice, pair, W, W), (slice, 3, W), (slice)
+  RaPartials part;  // K's blocks: the pairs
 };
 
 // Mcat_p[m][col] (0 past W or for a point past the slice); xs = (x, y, z, 1) of the point
@@ -178,25 +147,25 @@ __device__ __forceinline__ float ph_mcat(const PhArgs& a, int64_t p, bool ok, in
 }
 
 template <bool HESS>
-__global__ __launch_bounds__(PH_THREADS) void ph_reduced_kernel(const PhArgs a) {
-  __shared__ float s_MI[PH_DEPTH * PH_LS], s_MJ[PH_DEPTH * PH_LS], s_R[PH_DEPTH * PH_LS];
+__global__ __launch_bounds__(RA_THREADS) void ph_reduced_kernel(const PhArgs a) {
+  __shared__ float s_MI[PH_DEPTH * RA_LS], s_MJ[PH_DEPTH * RA_LS], s_R[PH_DEPTH * RA_LS];
   __shared__ float s_H[PH_PC * 81];
-  __shared__ float s_z[12 * PH_MAX_H];
+  __shared__ float s_z[12 * RA_MAX_H];
   __shared__ float s_F[PH_PC * 9], s_C[PH_PC * 9], s_P[PH_PC * 9], s_par[PH_PC * 4], s_x[PH_PC * 4], s_e[PH_PC];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t slice = blockIdx.x;
   const int ti = HESS ? (int)blockIdx.y / a.T : (int)blockIdx.y, tj = HESS ? (int)blockIdx.y % a.T : 0;
-  const int i0 = ti * PH_TILE, j0 = tj * PH_TILE, H = a.H, W = a.W;
+  const int i0 = ti * RA_TILE, j0 = tj * RA_TILE, H = a.H, W = a.W;
   const bool low = ti >= tj;              // on or under the diagonal: computes the three b == b' pairs too
   const bool sums_g = tj == 0, sums_e = ti == 0 && tj == 0;
   const float* MJ = (ti == tj) ? s_MI : s_MJ;
-  for (int e = t; e < 12 * H; e += PH_THREADS) s_z[e] = a.z[e];
+  for (int e = t; e < 12 * H; e += RA_THREADS) s_z[e] = a.z[e];
   const int64_t begin = slice * a.per, end = begin + a.per < a.N ? begin + a.per : a.N;
-  ph_f32x4 acc[PH_PAIRS][4];
+  ra_f32x4 acc[PH_PAIRS][4];
 #pragma unroll
   for (int pr = 0; pr < PH_PAIRS; ++pr)
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb) acc[pr][cb] = ph_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < 4; ++cb) acc[pr][cb] = ra_f32x4{0.f, 0.f, 0.f, 0.f};
   float g_acc = 0.0f, g_comp = 0.0f, e_acc = 0.0f, e_comp = 0.0f;
   const int pl = t / PH_TPP, sub = t % PH_TPP;
 
@@ -241,60 +210,56 @@ __global__ __launch_bounds__(PH_THREADS) void ph_reduced_kernel(const PhArgs a) 
       for (int k = 0; k < 9; ++k) s_F[pl * 9 + k] = F[k], s_C[pl * 9 + k] = C[k], s_P[pl * 9 + k] = fmaf(mu, F[k], as * C[k]);
       s_par[pl * 4] = mu, s_par[pl * 4 + 1] = lam, s_par[pl * 4 + 2] = as;
       s_x[pl * 4] = x0, s_x[pl * 4 + 1] = x1, s_x[pl * 4 + 2] = x2, s_x[pl * 4 + 3] = 1.0f;
-      if (sums_e) ph_add(e_acc, e_comp, ph_energy(F, J, mu, lam));
+      if (sums_e) ra_add(e_acc, e_comp, ph_energy(F, J, mu, lam));
     }
     __syncthreads();
     // (b) the Mcat images and the Hessian blocks
-    for (int e = t; e < PH_DEPTH * PH_TILE; e += PH_THREADS) {
+    for (int e = t; e < PH_DEPTH * RA_TILE; e += RA_THREADS) {
       const int d = e >> 6, c = e & 63, q = d / 3, m = d - q * 3;
       const bool ok = c0 + q < end;
-      s_MI[d * PH_LS + c] = ph_mcat(a, c0 + q, ok, m, i0 + c, s_x + q * 4);
-      if (HESS && ti != tj) s_MJ[d * PH_LS + c] = ph_mcat(a, c0 + q, ok, m, j0 + c, s_x + q * 4);
+      s_MI[d * RA_LS + c] = ph_mcat(a, c0 + q, ok, m, i0 + c, s_x + q * 4);
+      if (HESS && ti != tj) s_MJ[d * RA_LS + c] = ph_mcat(a, c0 + q, ok, m, j0 + c, s_x + q * 4);
     }
     if (HESS) {
-      for (int e = t; e < PH_PC * 81; e += PH_THREADS) {
+      for (int e = t; e < PH_PC * 81; e += RA_THREADS) {
         const int q = e / 81, rc = e - q * 81;
         s_H[e] = ph_hess_entry(s_F + q * 9, s_C + q * 9, s_par[q * 4], s_par[q * 4 + 1], s_par[q * 4 + 2], rc / 9, rc % 9);
       }
     }
     __syncthreads();
-    if (sums_g && t < 3 * PH_TILE) {
+    if (sums_g && t < 3 * RA_TILE) {
       const int b = t >> 6;  // per point, then the chunk's points pairwise, then onto the running sum with its error carried
       float v[PH_PC];
 #pragma unroll
       for (int q = 0; q < PH_PC; ++q) {
         const float* Pq = s_P + q * 9 + b * 3;
-        const float* Mq = s_MI + q * 3 * PH_LS + lane;
-        v[q] = fmaf(Pq[0], Mq[0], fmaf(Pq[1], Mq[PH_LS], Pq[2] * Mq[2 * PH_LS]));
+        const float* Mq = s_MI + q * 3 * RA_LS + lane;
+        v[q] = fmaf(Pq[0], Mq[0], fmaf(Pq[1], Mq[RA_LS], Pq[2] * Mq[2 * RA_LS]));
       }
-#pragma unroll
-      for (int w = 1; w < PH_PC; w <<= 1)
-#pragma unroll
-        for (int q = 0; q < PH_PC; q += 2 * w) v[q] = v[q] + v[q + w];
-      ph_add(g_acc, g_comp, v[0]);
+      ra_add(g_acc, g_comp, ra_pairwise(v));
     }
     if (HESS) {
 #pragma unroll
       for (int pr = 0; pr < PH_PAIRS; ++pr) {
         if (PH_B[pr] == PH_BP[pr] && !low) continue;
         // (c) R = H_p^{bb'} Mcat_p, column `lane`, points wave, wave + 4, ...
-        for (int q = wave; q < PH_PC; q += PH_THREADS / KAMD_WAVE) {
-          const float m0 = MJ[(q * 3) * PH_LS + lane], m1 = MJ[(q * 3 + 1) * PH_LS + lane], m2 = MJ[(q * 3 + 2) * PH_LS + lane];
+        for (int q = wave; q < PH_PC; q += RA_THREADS / KAMD_WAVE) {
+          const float m0 = MJ[(q * 3) * RA_LS + lane], m1 = MJ[(q * 3 + 1) * RA_LS + lane], m2 = MJ[(q * 3 + 2) * RA_LS + lane];
           const float* Hq = s_H + q * 81 + PH_B[pr] * 27 + PH_BP[pr] * 3;
 #pragma unroll
           for (int m = 0; m < 3; ++m)
-            s_R[(q * 3 + m) * PH_LS + lane] = fmaf(Hq[m * 9], m0, fmaf(Hq[m * 9 + 1], m1, Hq[m * 9 + 2] * m2));
+            s_R[(q * 3 + m) * RA_LS + lane] = fmaf(Hq[m * 9], m0, fmaf(Hq[m * 9 + 1], m1, Hq[m * 9 + 2] * m2));
         }
         __syncthreads();
         // (d) lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], D[row 4 (l >> 4) + reg][col l & 15]
         if (i0 + wave * 16 < W) {
           const int kq = lane >> 4, r = lane & 15;
           for (int d = 0; d < PH_DEPTH; d += 4) {
-            const float av = s_MI[(d + kq) * PH_LS + wave * 16 + r];
+            const float av = s_MI[(d + kq) * RA_LS + wave * 16 + r];
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
               if (j0 + cb * 16 < W)
-                acc[pr][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, s_R[(d + kq) * PH_LS + cb * 16 + r], acc[pr][cb], 0, 0, 0);
+                acc[pr][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, s_R[(d + kq) * RA_LS + cb * 16 + r], acc[pr][cb], 0, 0, 0);
           }
         }
         __syncthreads();
@@ -306,7 +271,7 @@ __global__ __launch_bounds__(PH_THREADS) void ph_reduced_kernel(const PhArgs a) 
 #pragma unroll
     for (int pr = 0; pr < PH_PAIRS; ++pr) {
       if (PH_B[pr] == PH_BP[pr] && !low) continue;
-      float* P = a.Kp + ((size_t)slice * PH_PAIRS + pr) * (size_t)W * W;
+      float* P = a.part.Kp + ((size_t)slice * PH_PAIRS + pr) * (size_t)W * W;
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -316,79 +281,18 @@ __global__ __launch_bounds__(PH_THREADS) void ph_reduced_kernel(const PhArgs a) 
         }
     }
   }
-  if (sums_g && t < 3 * PH_TILE && i0 + lane < W) a.gp[((size_t)slice * 3 + (t >> 6)) * W + i0 + lane] = g_acc;
-  if (sums_e) {
-    __syncthreads();
-    if (sub == 0) s_e[pl] = e_acc;
-    __syncthreads();
-    if (t == 0) {
-      float sum = 0.0f, comp = 0.0f;
-      for (int q = 0; q < PH_PC; ++q) ph_add(sum, comp, s_e[q]);
-      a.ep[slice] = sum;
-    }
-  }
+  if (sums_g && t < 3 * RA_TILE && i0 + lane < W) a.part.gp[((size_t)slice * 3 + (t >> 6)) * W + i0 + lane] = g_acc;
+  if (sums_e) ra_slice_energy<PH_PC>(e_acc, sub == 0, pl, s_e, a.part.ep + slice);
 }
 
-// the slices' partials added in index order -> K (D, D) (nullptr: none), g (D), E (1); D = 12 H, row = 12 h + 4 b + n
-__global__ __launch_bounds__(256) void ph_finish_kernel(int slices, int H, const float* __restrict__ Kp, const float* __restrict__ gp,
-                                                        const float* __restrict__ ep, float* __restrict__ K, float* __restrict__ g,
-                                                        float* __restrict__ E) {
-  const int64_t D = 12 * (int64_t)H, W = 4 * (int64_t)H;
-  const int64_t nK = K != nullptr ? D * D : 0, total = nK + D + 1;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const float* src;
-    int64_t step;
-    if (e < nK) {
-      const int64_t r = e / D, c = e - r * D;
-      int b = (int)(r % 12) / 4, bp = (int)(c % 12) / 4;
-      int64_t i = (r / 12) * 4 + (r & 3), j = (c / 12) * 4 + (c & 3);
-      if (b < bp || (b == bp && i < j)) {  // the mirrored entry
-        const int sb = b;
-        const int64_t si = i;
-        b = bp, bp = sb, i = j, j = si;
-      }
-      src = Kp + ((size_t)(b * (b + 1) / 2 + bp) * W + i) * W + j;
-      step = PH_PAIRS * W * W;
-    } else if (e < nK + D) {
-      const int64_t r = e - nK;
-      src = gp + ((r % 12) / 4) * W + (r / 12) * 4 + (r & 3);
-      step = 3 * W;
-    } else {
-      src = ep;
-      step = 1;
-    }
-    float sum = src[0];
-    for (int s = 1; s < slices; ++s) sum = sum + src[(size_t)s * step];
-    if (e < nK)
-      K[e] = sum;
-    else if (e < nK + D)
-      g[e - nK] = sum;
-    else
-      E[0] = sum;
-  }
-}
-
-inline int ph_material_blocks(int64_t N) {
-  const int64_t blocks = (N + KAMD_WAVE - 1) / KAMD_WAVE;
-  return (int)(blocks < PH_PT_BLOCKS ? blocks : PH_PT_BLOCKS);
-}
-inline int ph_tiles(int H) { return (4 * H + PH_TILE - 1) / PH_TILE; }
-inline int64_t ph_slice_points(int64_t N, int H) {
-  const int64_t tiles = (int64_t)ph_tiles(H) * ph_tiles(H);
-  int64_t slices = (PH_TARGET_GROUPS + tiles - 1) / tiles;
-  if (slices > PH_MAX_SLICES) slices = PH_MAX_SLICES;
-  int64_t per = ((N + slices - 1) / slices + PH_PC - 1) / PH_PC * PH_PC;
-  return per < PH_MIN_SLICE ? PH_MIN_SLICE : per;
-}
-inline bool ph_sizes_ok(int64_t N, int H) { return N >= 0 && N <= 0x7FFFFFFFLL && H >= 1 && H <= PH_MAX_H; }
-inline int64_t ph_slices(int64_t N, int H) { return (N + ph_slice_points(N, H) - 1) / ph_slice_points(N, H); }
+inline int64_t ph_slice_points(int64_t N, int H) { return ra_slice_len(N, ra_tiles(H) * ra_tiles(H), PH_PC, PH_MAX_SLICES); }
 
 }  // namespace
 
 extern "C" {
 
 size_t kamd_physics_neohookean_workspace(int64_t N) {
-  return N > 0 ? kamd_align16((size_t)ph_material_blocks(N) * sizeof(float)) : 0;
+  return N > 0 ? kamd_align16((size_t)ra_term_blocks(N, KAMD_WAVE) * sizeof(float)) : 0;
 }
 
 int kamd_physics_neohookean_f32(void* stream, int64_t N, const float* defo_grads, const float* mu, const float* lam, const float* vol,
@@ -398,56 +302,41 @@ int kamd_physics_neohookean_f32(void* stream, int64_t N, const float* defo_grads
   if (defo_grads == nullptr || mu == nullptr || lam == nullptr || vol == nullptr || (energy != nullptr && workspace == nullptr))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const int blocks = ph_material_blocks(N);
+  const int blocks = ra_term_blocks(N, KAMD_WAVE);
   float* partial = energy != nullptr ? (float*)workspace : nullptr;
   hipLaunchKernelGGL(ph_material_kernel, dim3((unsigned)blocks), dim3(KAMD_WAVE), 0, st, N, defo_grads, mu, lam, vol, coeff, partial,
                      gradient, hessian);
-  if (energy != nullptr) hipLaunchKernelGGL(ph_sum_kernel, dim3(1), dim3(KAMD_WAVE), 0, st, blocks, (const float*)partial, energy);
+  if (energy != nullptr) hipLaunchKernelGGL(ra_sum_kernel, dim3(1), dim3(KAMD_WAVE), 0, st, blocks, (const float*)partial, energy);
   KAMD_RETURN_LAST_ERROR();
 }
 
 int kamd_physics_chunk_points(void) { return PH_PC; }
-int kamd_physics_max_handles(void) { return PH_MAX_H; }
-int64_t kamd_physics_slice_points(int64_t N, int H) { return ph_sizes_ok(N, H) ? ph_slice_points(N, H) : 0; }
+int kamd_physics_max_handles(void) { return RA_MAX_H; }
+int64_t kamd_physics_slice_points(int64_t N, int H) { return ra_sizes_ok(N, H) ? ph_slice_points(N, H) : 0; }
 
 size_t kamd_physics_reduced_workspace(int64_t N, int H, int hessian) {
-  if (!ph_sizes_ok(N, H) || N == 0) return 0;
-  const size_t S = (size_t)ph_slices(N, H), W = 4 * (size_t)H;
-  return (hessian ? kamd_align16(S * PH_PAIRS * W * W * sizeof(float)) : 0) + kamd_align16(S * 3 * W * sizeof(float)) +
-         kamd_align16(S * sizeof(float));
+  if (!ra_sizes_ok(N, H) || N == 0) return 0;
+  return ra_workspace(ra_slices(N, ph_slice_points(N, H)), PH_PAIRS, H, hessian);
 }
 
 int kamd_physics_reduced_neohookean_f32(void* stream, int64_t N, int H, const float* z, const float* pts, const float* weights,
                                         const float* weights_jac, const float* mu, const float* lam, const float* vol, float coeff,
                                         int hessian, float* E, float* g, float* K, void* workspace, size_t workspace_bytes) {
-  if (!ph_sizes_ok(N, H) || N == 0) return (int)hipErrorInvalidValue;
+  if (!ra_sizes_ok(N, H) || N == 0) return (int)hipErrorInvalidValue;
   if (z == nullptr || pts == nullptr || weights == nullptr || weights_jac == nullptr || mu == nullptr || lam == nullptr ||
       vol == nullptr || E == nullptr || g == nullptr || (hessian && K == nullptr) || workspace == nullptr ||
       workspace_bytes < kamd_physics_reduced_workspace(N, H, hessian))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const size_t S = (size_t)ph_slices(N, H), W = 4 * (size_t)H;
-  char* ws = (char*)workspace;
   PhArgs a;
   a.z = z, a.pts = pts, a.w = weights, a.wj = weights_jac, a.mu = mu, a.lam = lam, a.vol = vol, a.coeff = coeff;
-  a.N = N, a.per = ph_slice_points(N, H), a.H = H, a.W = (int)W, a.T = ph_tiles(H);
-  a.Kp = nullptr;
-  if (hessian) {
-    a.Kp = (float*)ws;
-    ws += kamd_align16(S * PH_PAIRS * W * W * sizeof(float));
-  }
-  a.gp = (float*)ws;
-  ws += kamd_align16(S * 3 * W * sizeof(float));
-  a.ep = (float*)ws;
+  a.N = N, a.per = ph_slice_points(N, H), a.H = H, a.W = 4 * H, a.T = ra_tiles(H);
+  const size_t S = ra_slices(N, a.per);
+  ra_workspace(S, PH_PAIRS, H, hessian, workspace, &a.part);
   if (hessian)
-    hipLaunchKernelGGL(ph_reduced_kernel<true>, dim3((unsigned)S, (unsigned)(a.T * a.T)), dim3(PH_THREADS), 0, st, a);
+    hipLaunchKernelGGL(ph_reduced_kernel<true>, dim3((unsigned)S, (unsigned)(a.T * a.T)), dim3(RA_THREADS), 0, st, a);
   else
-    hipLaunchKernelGGL(ph_reduced_kernel<false>, dim3((unsigned)S, (unsigned)a.T), dim3(PH_THREADS), 0, st, a);
-  const int64_t D = 12 * (int64_t)H, total = (hessian ? D * D : 0) + D + 1;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > (int64_t)KAMD_NUM_CU * 16) blocks = (int64_t)KAMD_NUM_CU * 16;
-  hipLaunchKernelGGL(ph_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (int)S, H, (const float*)a.Kp, (const float*)a.gp,
-                     (const float*)a.ep, hessian ? K : (float*)nullptr, g, E);
-  KAMD_RETURN_LAST_ERROR();
+    hipLaunchKernelGGL(ph_reduced_kernel<false>, dim3((unsigned)S, (unsigned)a.T), dim3(RA_THREADS), 0, st, a);
+  return ra_finish<RaSymmetricSix>(st, S, H, a.part, hessian ? K : nullptr, g, E);
 }
 }

@@ -21,40 +21,28 @@
 //      g[h][b][n]  = sum_rows f[b] m[4 h + n]
 //      K_bb[i][j]  = sum_rows d[b] m[i] m[j]        three symmetric W x W rank updates of depth N + pins; K_bb' = 0 for b != b'
 //    The row stream is the N points, then the pins (a pin row gathers x0 and the weights of its point; a pin index outside [0, N)
-//    reads nothing and is a row of zeros).  Grid (slice of rows, 64 x 64 tile of W x W on or under the diagonal), 256 threads.  The
-//    workgroup walks its slice in chunks of SF_CR = 32 rows.  Per chunk:
+//    reads nothing and is a row of zeros).  The grid (tiles on or under the diagonal), the sums of g and E, the slices' partials and
+//    their finish are those of reduced_assembly.h; the partials hold the three blocks of RaDiagonalThree, and the finish writes the
+//    zero blocks.  The workgroup walks its slice in chunks of SF_CR = 32 rows.  Per chunk:
 //      (a) z and delta are in LDS (staged once)
 //      (b) 16 lanes per row (two passes of 16 rows) accumulate dx_p and u_p over the handles h = lane, lane + 16, ... and add up by
 //          a butterfly inside their row of 16; the first lane classifies the floor and leaves e (kept), f, d, (x0, 1) and the
 //          point's index in LDS
 //      (c) all threads write the images of m, rows x 64 columns of the row tile and of the column tile (a diagonal tile: one image)
-//      (d) for each axis b: acc[b] += (d[b] m_row)^T m_col by v_mfma_f32_16x16x4_f32, the A operand scaled in the register: no
-//          scaled image, no barrier between the axes.  Wavefront w owns rows 16 w ... 16 w + 15 of the tile and four 16-column
-//          blocks: 3 x 4 x 4 = 48 accumulator registers.  Blocks past W, and in a diagonal tile above the diagonal, are skipped.
-//      g: the workgroups of column tile 0 (thread = (b, column): the chunk's rows pairwise, chunks by a compensated sum: a
-//         sequential chain of that many terms missed its bound in physics.hip); E: tile (0, 0), compensated in the rows' first lanes.
-//    Each slice stores ONE partial of K, g and E; sf_finish_kernel adds the slices in index order, mirrors (entries (i, j) and
-//    (j, i) read the same partials: K is symmetric to the bit), scatters into the (12 H, 12 H) layout and writes the zero blocks.
+//      (d) for each axis b: acc[b] += (d[b] m_row)^T m_col, the A operand scaled in the register: no scaled image, no barrier
+//          between the axes; 3 x 4 x 4 = 48 accumulator registers.  Blocks past W, and in a diagonal tile above the diagonal, are skipped.
+//      g: f[b] m of the row tile; E: e, in the rows' first lanes.
 //    HESS = false (a line search's energy and gradient): grid (slice, row tile), no column image, no MFMA.
 //    LDS: 2 images of 32 x 80 floats (20 KiB) + z, delta 96 H bytes (12 KiB reserved) + f, d, x, index 1.4 KiB.
-#include "common.h"
+#include "reduced_assembly.h"
 #include "../../include/kaolin_amd.h"
 
 namespace {
 
-typedef float sf_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SF_THREADS = 256;
-constexpr int SF_TERM_BLOCKS = 1024;           // most workgroups (= energy partials) of the per-point kernel
 constexpr int SF_CR = 32;                      // rows per chunk = GEMM depth of a chunk
 constexpr int SF_TPR = 16;                     // lanes per row in stage (b)
-constexpr int SF_PASS = SF_THREADS / SF_TPR;   // rows of one pass of stage (b)
-constexpr int SF_TILE = 64;
-constexpr int SF_LS = SF_TILE + 16;            // LDS row stride: lanes l and l + 16 read rows 80 dwords apart -> other banks
-constexpr int SF_MAX_H = 128;                  // = kamd_physics_max_handles()
-constexpr int SF_MIN_SLICE = 4 * SF_CR;
+constexpr int SF_PASS = RA_THREADS / SF_TPR;   // rows of one pass of stage (b)
 constexpr int SF_MAX_SLICES = 128;
-constexpr int SF_TARGET_GROUPS = 512;          // slices x tiles aimed at: two workgroups per CU
 
 // the terms that live on the points; a null first pointer: that term is absent
 struct SfScene {
@@ -68,17 +56,6 @@ struct SfScene {
   const float* mass;         // inertia
 };
 
-// sum += v with the rounding error of every earlier step carried in `comp` (Kahan; nothing here may be reassociated)
-__device__ __forceinline__ void sf_add(float& sum, float& comp, float v) {
-  const float y = v - comp, t = sum + y;
-  comp = (t - sum) - y;
-  sum = t;
-}
-__device__ __forceinline__ float sf_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < KAMD_WAVE; m <<= 1) v = v + __shfl_xor(v, m);
-  return v;
-}
 __device__ __forceinline__ float sf_dot(const float* u, const float* v) { return fmaf(u[0], v[0], fmaf(u[1], v[1], u[2] * v[2])); }
 
 // e, f, d of point p at x, u = B_p delta
@@ -128,11 +105,10 @@ struct SfPins {
 
 // MODE 0: energy partials, 1: gradient (N, 3), 2: Hessian (N, 3, 3)
 template <int MODE>
-__global__ __launch_bounds__(SF_THREADS) void sf_terms_kernel(const SfScene s, const SfPins k, const float* __restrict__ dx,
+__global__ __launch_bounds__(RA_THREADS) void sf_terms_kernel(const SfScene s, const SfPins k, const float* __restrict__ dx,
                                                               float* __restrict__ out) {
-  __shared__ float s_w[SF_THREADS / KAMD_WAVE];
   float e_acc = 0.0f, e_comp = 0.0f;
-  for (int64_t p = (int64_t)blockIdx.x * SF_THREADS + threadIdx.x; p < s.N; p += (int64_t)gridDim.x * SF_THREADS) {
+  for (int64_t p = (int64_t)blockIdx.x * RA_THREADS + threadIdx.x; p < s.N; p += (int64_t)gridDim.x * RA_THREADS) {
     const float x[3] = {s.x0[p * 3] + dx[p * 3], s.x0[p * 3 + 1] + dx[p * 3 + 1], s.x0[p * 3 + 2] + dx[p * 3 + 2]};
     const float u[3] = {0.0f, 0.0f, 0.0f};
     float e = 0.0f, f[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f};
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_terms_kernel(const SfScene s, c
     } else {
       e = sf_point(s, p, x, u, f, d);
     }
-    if (MODE == 0) sf_add(e_acc, e_comp, e);
+    if (MODE == 0) ra_add(e_acc, e_comp, e);
     if (MODE == 1) {
 #pragma unroll
       for (int b = 0; b < 3; ++b) out[p * 3 + b] = f[b];
@@ -161,19 +137,7 @@ __global__ __launch_bounds__(SF_THREADS) void sf_terms_kernel(const SfScene s, c
       for (int j = 0; j < 9; ++j) out[p * 9 + j] = (j % 4 == 0) ? d[j / 4] : 0.0f;
     }
   }
-  if (MODE == 0) {
-    e_acc = sf_wave_sum(e_acc);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = e_acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-  }
-}
-// out[0] = the partials added in index order
-__global__ __launch_bounds__(KAMD_WAVE) void sf_sum_kernel(int n, const float* __restrict__ partial, float* __restrict__ out) {
-  if (threadIdx.x != 0) return;
-  float sum = 0.0f, comp = 0.0f;
-  for (int k = 0; k < n; ++k) sf_add(sum, comp, partial[k]);
-  out[0] = sum;
+  if (MODE == 0) ra_block_energy(e_acc, out);
 }
 
 // ---- 2. the reduced terms ---------------------------------------------------------------------------------------------------------------
@@ -185,7 +149,7 @@ struct SfArgs {
   const float *z, *zp, *zd, *w;    // (12 H) each (zp == nullptr: no inertia), (N, H)
   float dt;
   int H, W;                        // handles, 4 H
-  float *Kp, *gp, *ep;             // partials (slice, 3, W, W), (slice, 3, W), (slice)
+  RaPartials part;                 // K's blocks: the axes
 };
 
 // m of the chunk's row q at column col (0 past W and for a row past the slice or without a point)
@@ -196,34 +160,30 @@ __device__ __forceinline__ float sf_m(const SfArgs& a, const int* s_p, const flo
 }
 
 template <bool HESS>
-__global__ __launch_bounds__(SF_THREADS) void sf_reduced_kernel(const SfArgs a) {
-  __shared__ float s_MI[SF_CR * SF_LS], s_MJ[HESS ? SF_CR * SF_LS : 1];
-  __shared__ float s_z[12 * SF_MAX_H], s_dl[12 * SF_MAX_H];
+__global__ __launch_bounds__(RA_THREADS) void sf_reduced_kernel(const SfArgs a) {
+  __shared__ float s_MI[SF_CR * RA_LS], s_MJ[HESS ? SF_CR * RA_LS : 1];
+  __shared__ float s_z[12 * RA_MAX_H], s_dl[12 * RA_MAX_H];
   __shared__ float s_f[SF_CR * 3], s_d[SF_CR * 3], s_x[SF_CR * 4], s_e[SF_PASS];
   __shared__ int s_p[SF_CR];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t slice = blockIdx.x;
   int ti = (int)blockIdx.y, tj = 0;
-  if (HESS) {   // tile blockIdx.y of the lower triangle, row by row
-    ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.y) ++ti;
-    tj = (int)blockIdx.y - ti * (ti + 1) / 2;
-  }
-  const int i0 = ti * SF_TILE, j0 = tj * SF_TILE, H = a.H, W = a.W;
+  if (HESS) ra_lower_tile((int)blockIdx.y, ti, tj);
+  const int i0 = ti * RA_TILE, j0 = tj * RA_TILE, H = a.H, W = a.W;
   const bool diag = ti == tj, sums_g = tj == 0, sums_e = ti == 0 && tj == 0, inertia = a.zp != nullptr;
   const float* MJ = diag ? s_MI : s_MJ;
   const int64_t N = a.s.N, rows = N + a.P;
   const int64_t begin = slice * a.per, end = begin + a.per < rows ? begin + a.per : rows;
-  for (int e = t; e < 12 * H; e += SF_THREADS) {
+  for (int e = t; e < 12 * H; e += RA_THREADS) {
     const float zv = a.z[e];
     s_z[e] = zv;
     s_dl[e] = inertia ? (zv - a.zp[e]) - a.dt * a.zd[e] : 0.0f;
   }
-  sf_f32x4 acc[3][4];
+  ra_f32x4 acc[3][4];
 #pragma unroll
   for (int b = 0; b < 3; ++b)
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb) acc[b][cb] = sf_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < 4; ++cb) acc[b][cb] = ra_f32x4{0.f, 0.f, 0.f, 0.f};
   float g_acc = 0.0f, g_comp = 0.0f, e_acc = 0.0f, e_comp = 0.0f;
   const int pl = t / SF_TPR, sub = t % SF_TPR;
 
@@ -280,40 +240,36 @@ __global__ __launch_bounds__(SF_THREADS) void sf_reduced_kernel(const SfArgs a) 
         for (int b = 0; b < 3; ++b) s_f[q * 3 + b] = f[b], s_d[q * 3 + b] = d[b], s_x[q * 4 + b] = xr[b];
         s_x[q * 4 + 3] = 1.0f;
         s_p[q] = (int)p;
-        if (sums_e) sf_add(e_acc, e_comp, e);
+        if (sums_e) ra_add(e_acc, e_comp, e);
       }
     }
     __syncthreads();
     // (c) the images of m
-    for (int e = t; e < SF_CR * SF_TILE; e += SF_THREADS) {
+    for (int e = t; e < SF_CR * RA_TILE; e += RA_THREADS) {
       const int q = e >> 6, col = e & 63;
-      s_MI[q * SF_LS + col] = sf_m(a, s_p, s_x, q, i0 + col);
-      if (HESS && !diag) s_MJ[q * SF_LS + col] = sf_m(a, s_p, s_x, q, j0 + col);
+      s_MI[q * RA_LS + col] = sf_m(a, s_p, s_x, q, i0 + col);
+      if (HESS && !diag) s_MJ[q * RA_LS + col] = sf_m(a, s_p, s_x, q, j0 + col);
     }
     __syncthreads();
-    if (sums_g && t < 3 * SF_TILE) {
+    if (sums_g && t < 3 * RA_TILE) {
       const int b = t >> 6;  // per row, then the chunk's rows pairwise, then onto the running sum with its error carried
       float v[SF_CR];
 #pragma unroll
-      for (int q = 0; q < SF_CR; ++q) v[q] = s_f[q * 3 + b] * s_MI[q * SF_LS + lane];
-#pragma unroll
-      for (int w = 1; w < SF_CR; w <<= 1)
-#pragma unroll
-        for (int q = 0; q < SF_CR; q += 2 * w) v[q] = v[q] + v[q + w];
-      sf_add(g_acc, g_comp, v[0]);
+      for (int q = 0; q < SF_CR; ++q) v[q] = s_f[q * 3 + b] * s_MI[q * RA_LS + lane];
+      ra_add(g_acc, g_comp, ra_pairwise(v));
     }
     // (d) lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], D[row 4 (l >> 4) + reg][col l & 15]
     if (HESS && i0 + wave * 16 < W) {
       const int kq = lane >> 4, rr = lane & 15;
       for (int d = 0; d < SF_CR; d += 4) {
-        const float av = s_MI[(d + kq) * SF_LS + wave * 16 + rr];
+        const float av = s_MI[(d + kq) * RA_LS + wave * 16 + rr];
         float as[3];
 #pragma unroll
         for (int b = 0; b < 3; ++b) as[b] = av * s_d[(d + kq) * 3 + b];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
           if (j0 + cb * 16 < W && (!diag || cb <= wave)) {
-            const float bv = MJ[(d + kq) * SF_LS + cb * 16 + rr];
+            const float bv = MJ[(d + kq) * RA_LS + cb * 16 + rr];
 #pragma unroll
             for (int b = 0; b < 3; ++b) acc[b][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(as[b], bv, acc[b][cb], 0, 0, 0);
           }
@@ -322,90 +278,13 @@ __global__ __launch_bounds__(SF_THREADS) void sf_reduced_kernel(const SfArgs a) 
   }
 
   if (HESS) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      float* P = a.Kp + ((size_t)slice * 3 + b) * (size_t)W * W;
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-        if (!diag || cb <= wave) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int row = i0 + wave * 16 + (lane >> 4) * 4 + j, col = j0 + cb * 16 + (lane & 15);
-            if (row < W && col < W) P[(size_t)row * W + col] = acc[b][cb][j];
-          }
-        }
-    }
+    ra_store_blocks(acc, a.part.Kp, slice, W, i0, j0, wave, lane, diag);
   }
-  if (sums_g && t < 3 * SF_TILE && i0 + lane < W) a.gp[((size_t)slice * 3 + (t >> 6)) * W + i0 + lane] = g_acc;
-  if (sums_e) {
-    __syncthreads();
-    if (sub == 0) s_e[pl] = e_acc;
-    __syncthreads();
-    if (t == 0) {
-      float sum = 0.0f, comp = 0.0f;
-      for (int q = 0; q < SF_PASS; ++q) sf_add(sum, comp, s_e[q]);
-      a.ep[slice] = sum;
-    }
-  }
+  if (sums_g && t < 3 * RA_TILE && i0 + lane < W) a.part.gp[((size_t)slice * 3 + (t >> 6)) * W + i0 + lane] = g_acc;
+  if (sums_e) ra_slice_energy<SF_PASS>(e_acc, sub == 0, pl, s_e, a.part.ep + slice);
 }
 
-// the slices' partials added in index order -> K (D, D) (nullptr: none), g (D), E (1); D = 12 H, row = 12 h + 4 b + n
-__global__ __launch_bounds__(256) void sf_finish_kernel(int slices, int H, const float* __restrict__ Kp, const float* __restrict__ gp,
-                                                        const float* __restrict__ ep, float* __restrict__ K, float* __restrict__ g,
-                                                        float* __restrict__ E) {
-  const int64_t D = 12 * (int64_t)H, W = 4 * (int64_t)H;
-  const int64_t nK = K != nullptr ? D * D : 0, total = nK + D + 1;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const float* src;
-    int64_t step;
-    if (e < nK) {
-      const int64_t rw = e / D, c = e - rw * D;
-      const int b = (int)(rw % 12) / 4, bp = (int)(c % 12) / 4;
-      if (b != bp) {   // the axes do not couple
-        K[e] = 0.0f;
-        continue;
-      }
-      int64_t i = (rw / 12) * 4 + (rw & 3), j = (c / 12) * 4 + (c & 3);
-      if (i < j) {  // the mirrored entry of the same block
-        const int64_t si = i;
-        i = j, j = si;
-      }
-      src = Kp + ((size_t)b * W + i) * W + j;
-      step = 3 * W * W;
-    } else if (e < nK + D) {
-      const int64_t rw = e - nK;
-      src = gp + ((rw % 12) / 4) * W + (rw / 12) * 4 + (rw & 3);
-      step = 3 * W;
-    } else {
-      src = ep;
-      step = 1;
-    }
-    float sum = src[0];
-    for (int s = 1; s < slices; ++s) sum = sum + src[(size_t)s * step];
-    if (e < nK)
-      K[e] = sum;
-    else if (e < nK + D)
-      g[e - nK] = sum;
-    else
-      E[0] = sum;
-  }
-}
-
-inline int sf_term_blocks(int64_t N) {
-  const int64_t blocks = (N + SF_THREADS - 1) / SF_THREADS;
-  return (int)(blocks < SF_TERM_BLOCKS ? blocks : SF_TERM_BLOCKS);
-}
-inline int sf_tiles(int H) { return (4 * H + SF_TILE - 1) / SF_TILE; }
-inline int sf_tri(int T) { return T * (T + 1) / 2; }
-inline int64_t sf_slice_rows(int64_t rows, int H) {
-  const int64_t tiles = sf_tri(sf_tiles(H));
-  int64_t slices = (SF_TARGET_GROUPS + tiles - 1) / tiles;
-  if (slices > SF_MAX_SLICES) slices = SF_MAX_SLICES;
-  const int64_t per = ((rows + slices - 1) / slices + SF_CR - 1) / SF_CR * SF_CR;
-  return per < SF_MIN_SLICE ? SF_MIN_SLICE : per;
-}
-inline bool sf_sizes_ok(int64_t rows, int H) { return rows >= 0 && rows <= 0x7FFFFFFFLL && H >= 1 && H <= SF_MAX_H; }
-inline int64_t sf_slices(int64_t rows, int H) { return (rows + sf_slice_rows(rows, H) - 1) / sf_slice_rows(rows, H); }
+inline int64_t sf_slice_rows(int64_t rows, int H) { return ra_slice_len(rows, ra_tri(ra_tiles(H)), SF_CR, SF_MAX_SLICES); }
 inline SfScene sf_scene(int64_t N, const float* x0, const float* rho, const float* gvol, float gx, float gy, float gz, float cg,
                         const float* fvol, float fh, int axis, int flip, float cf, const float* mass) {
   SfScene s;
@@ -418,7 +297,7 @@ inline SfScene sf_scene(int64_t N, const float* x0, const float* rho, const floa
 
 extern "C" {
 
-size_t kamd_scene_terms_workspace(int64_t N) { return N > 0 ? kamd_align16((size_t)sf_term_blocks(N) * sizeof(float)) : 0; }
+size_t kamd_scene_terms_workspace(int64_t N) { return N > 0 ? kamd_align16((size_t)ra_term_blocks(N, RA_THREADS) * sizeof(float)) : 0; }
 
 int kamd_scene_terms_f32(void* stream, int64_t N, const float* dx, const float* x0, const float* rho, const float* gvol, float gx,
                          float gy, float gz, const float* fvol, float floor_height, int floor_axis, int flip_floor, int64_t P,
@@ -435,24 +314,22 @@ int kamd_scene_terms_f32(void* stream, int64_t N, const float* dx, const float* 
   const SfScene s = sf_scene(N, x0, rho, gvol, gx, gy, gz, coeff, fvol, floor_height, floor_axis, flip_floor, coeff, nullptr);
   SfPins k;
   k.P = P, k.sorted = pins_sorted, k.order = pins_order, k.y = pinned_x, k.c = coeff;
-  const int blocks = sf_term_blocks(N);
+  const int blocks = ra_term_blocks(N, RA_THREADS);
   if (energy != nullptr) {
-    hipLaunchKernelGGL(sf_terms_kernel<0>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, st, s, k, dx, (float*)workspace);
-    hipLaunchKernelGGL(sf_sum_kernel, dim3(1), dim3(KAMD_WAVE), 0, st, blocks, (const float*)workspace, energy);
+    hipLaunchKernelGGL(sf_terms_kernel<0>, dim3((unsigned)blocks), dim3(RA_THREADS), 0, st, s, k, dx, (float*)workspace);
+    hipLaunchKernelGGL(ra_sum_kernel, dim3(1), dim3(KAMD_WAVE), 0, st, blocks, (const float*)workspace, energy);
   }
-  if (gradient != nullptr) hipLaunchKernelGGL(sf_terms_kernel<1>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, st, s, k, dx, gradient);
-  if (hessian != nullptr) hipLaunchKernelGGL(sf_terms_kernel<2>, dim3((unsigned)blocks), dim3(SF_THREADS), 0, st, s, k, dx, hessian);
+  if (gradient != nullptr) hipLaunchKernelGGL(sf_terms_kernel<1>, dim3((unsigned)blocks), dim3(RA_THREADS), 0, st, s, k, dx, gradient);
+  if (hessian != nullptr) hipLaunchKernelGGL(sf_terms_kernel<2>, dim3((unsigned)blocks), dim3(RA_THREADS), 0, st, s, k, dx, hessian);
   KAMD_RETURN_LAST_ERROR();
 }
 
 int kamd_scene_chunk_rows(void) { return SF_CR; }
-int64_t kamd_scene_slice_rows(int64_t rows, int H) { return sf_sizes_ok(rows, H) ? sf_slice_rows(rows, H) : 0; }
+int64_t kamd_scene_slice_rows(int64_t rows, int H) { return ra_sizes_ok(rows, H) ? sf_slice_rows(rows, H) : 0; }
 
 size_t kamd_scene_reduced_workspace(int64_t rows, int H, int hessian) {
-  if (!sf_sizes_ok(rows, H) || rows == 0) return 0;
-  const size_t S = (size_t)sf_slices(rows, H), W = 4 * (size_t)H;
-  return (hessian ? kamd_align16(S * 3 * W * W * sizeof(float)) : 0) + kamd_align16(S * 3 * W * sizeof(float)) +
-         kamd_align16(S * sizeof(float));
+  if (!ra_sizes_ok(rows, H) || rows == 0) return 0;
+  return ra_workspace(ra_slices(rows, sf_slice_rows(rows, H)), RaDiagonalThree::BLOCKS, H, hessian);
 }
 
 int kamd_scene_reduced_f32(void* stream, int64_t N, int64_t P, int H, const float* z, const float* x0, const float* weights,
@@ -461,7 +338,7 @@ int kamd_scene_reduced_f32(void* stream, int64_t N, int64_t P, int H, const floa
                            const float* pinned_x, const float* pinned_coeff, const float* mass, const float* z_prev,
                            const float* z_dot, float dt, int hessian, float* E, float* g, float* K, void* workspace,
                            size_t workspace_bytes) {
-  if (N < 0 || P < 0 || N > 0x7FFFFFFFLL || P > 0x7FFFFFFFLL || !sf_sizes_ok(N + P, H) || N + P == 0)
+  if (N < 0 || P < 0 || N > 0x7FFFFFFFLL || P > 0x7FFFFFFFLL || !ra_sizes_ok(N + P, H) || N + P == 0)
     return (int)hipErrorInvalidValue;
   if (z == nullptr || x0 == nullptr || weights == nullptr || (rho != nullptr && gvol == nullptr) ||
       (fvol != nullptr && (floor_axis < 0 || floor_axis > 2)) ||
@@ -470,30 +347,17 @@ int kamd_scene_reduced_f32(void* stream, int64_t N, int64_t P, int H, const floa
       workspace == nullptr || workspace_bytes < kamd_scene_reduced_workspace(N + P, H, hessian))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const size_t S = (size_t)sf_slices(N + P, H), W = 4 * (size_t)H;
-  char* ws = (char*)workspace;
   SfArgs a;
   a.s = sf_scene(N, x0, rho, gvol, gx, gy, gz, gravity_coeff, fvol, floor_height, floor_axis, flip_floor, floor_coeff, mass);
   a.P = P, a.per = sf_slice_rows(N + P, H), a.pin_idx = pinned_indices, a.pin_y = pinned_x, a.pin_c = pinned_coeff;
-  a.z = z, a.zp = mass != nullptr ? z_prev : nullptr, a.zd = z_dot, a.w = weights, a.dt = dt, a.H = H, a.W = (int)W;
-  a.Kp = nullptr;
-  if (hessian) {
-    a.Kp = (float*)ws;
-    ws += kamd_align16(S * 3 * W * W * sizeof(float));
-  }
-  a.gp = (float*)ws;
-  ws += kamd_align16(S * 3 * W * sizeof(float));
-  a.ep = (float*)ws;
-  const int T = sf_tiles(H);
+  a.z = z, a.zp = mass != nullptr ? z_prev : nullptr, a.zd = z_dot, a.w = weights, a.dt = dt, a.H = H, a.W = 4 * H;
+  const size_t S = ra_slices(N + P, a.per);
+  ra_workspace(S, RaDiagonalThree::BLOCKS, H, hessian, workspace, &a.part);
+  const int T = ra_tiles(H);
   if (hessian)
-    hipLaunchKernelGGL(sf_reduced_kernel<true>, dim3((unsigned)S, (unsigned)sf_tri(T)), dim3(SF_THREADS), 0, st, a);
+    hipLaunchKernelGGL(sf_reduced_kernel<true>, dim3((unsigned)S, (unsigned)ra_tri(T)), dim3(RA_THREADS), 0, st, a);
   else
-    hipLaunchKernelGGL(sf_reduced_kernel<false>, dim3((unsigned)S, (unsigned)T), dim3(SF_THREADS), 0, st, a);
-  const int64_t D = 12 * (int64_t)H, total = (hessian ? D * D : 0) + D + 1;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > (int64_t)KAMD_NUM_CU * 16) blocks = (int64_t)KAMD_NUM_CU * 16;
-  hipLaunchKernelGGL(sf_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (int)S, H, (const float*)a.Kp, (const float*)a.gp,
-                     (const float*)a.ep, hessian ? K : (float*)nullptr, g, E);
-  KAMD_RETURN_LAST_ERROR();
+    hipLaunchKernelGGL(sf_reduced_kernel<false>, dim3((unsigned)S, (unsigned)T), dim3(RA_THREADS), 0, st, a);
+  return ra_finish<RaDiagonalThree>(st, S, H, a.part, hessian ? K : nullptr, g, E);
 }
 }

@@ -79,3 +79,40 @@ def test_workspace_queries_are_host_only_and_shape_driven():
     assert lib.kamd_rasterize_forward_workspace(1, 0, 1024, 50000, 4) == 0
     assert lib.kamd_trianglemeshes_to_voxelgrids_workspace(1, 30000, 4) > 0
     assert lib.kamd_deftet_forward_workspace(1, 50000, 4096, 4) > 0
+
+
+def test_reduced_slice_rule_and_workspace_formula():
+    """The three reduced (Simplicits) energies size their slices and their workspace by one rule (the shared reduced
+    assembly): slices = min(cap, ceil(512 / tiles)), per = max(4 chunk, ceil(ceil(count / slices) / chunk) chunk), and per slice
+    `blocks` W x W blocks of K (only with the Hessian), 3 W of g and one E, each part rounded up to 16 bytes.  Restated here."""
+    from kaolin_amd import _lib
+    lib = _lib.load()
+    assert lib.kamd_physics_max_handles() == 128
+
+    def tri(T):
+        return T * (T + 1) // 2
+
+    def align16(n):
+        return (n + 15) // 16 * 16
+
+    families = [   # slice query, workspace query, chunk, most slices, tiles of T a side, blocks of K per slice
+        (lib.kamd_physics_slice_points, lib.kamd_physics_reduced_workspace, lib.kamd_physics_chunk_points(), 16, 64, lambda T: T * T, 6),
+        (lib.kamd_collision_slice_contacts, lib.kamd_collision_reduced_workspace, lib.kamd_collision_chunk_contacts(), 32, 128, tri, 9),
+        (lib.kamd_scene_slice_rows, lib.kamd_scene_reduced_workspace, lib.kamd_scene_chunk_rows(), 32, 128, tri, 3),
+    ]
+    for slice_len, workspace, chunk_query, chunk, cap, tiles_of, blocks in families:
+        assert chunk_query == chunk
+        counts = [1, chunk - 1, chunk, chunk + 1, 4 * chunk, 4 * chunk + 1, 10 ** 5, 2 ** 31 - 1]
+        for H in (0, 129):
+            for count in counts:
+                assert slice_len(count, H) == 0 and workspace(count, H, 0) == 0 and workspace(count, H, 1) == 0, (H, count)
+        for H in range(1, 129):
+            W = 4 * H
+            slices = min(cap, -(-512 // tiles_of(-(-W // 64))))
+            for count in counts:
+                per = max(4 * chunk, -(-(-(-count // slices)) // chunk) * chunk)
+                assert slice_len(count, H) == per, (H, count)
+                S = -(-count // per)
+                small = align16(S * 3 * W * 4) + align16(S * 4)
+                assert workspace(count, H, 0) == small, (H, count)
+                assert workspace(count, H, 1) == align16(S * blocks * W * W * 4) + small, (H, count)

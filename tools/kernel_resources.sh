@@ -1,8 +1,10 @@
 #!/bin/bash
 # usage: tools/kernel_resources.sh <file.hip> [name filter]  -- registers / LDS / scratch per kernel (hipcc -Rpass-analysis)
+# The compile line is the Makefile's own for that object (`make -n`), per-file flags included: the build that ships.
 cd "$(dirname "$0")/../kaolin_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -fno-math-errno \
-  -Rpass-analysis=kernel-resource-usage ${KR_DEFS:-} -c "$1" -o /dev/null 2>&1 | python3 -c "
+obj="${1%.hip}.o"
+line=$(make -n -B "$obj" | grep -- "-c $1 ") || { echo "no rule compiles $1" >&2; exit 1; }
+${line% -o *} -o /dev/null -Rpass-analysis=kernel-resource-usage ${KR_DEFS:-} 2>&1 | python3 -c "
 import re,sys
 cur=None
 for line in sys.stdin:
