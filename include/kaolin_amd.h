@@ -1873,6 +1873,30 @@ int kamd_scene_reduced_f32(void* stream, int64_t N, int64_t P, int H, const floa
                            size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------- */
+/* The linear solve of a Newton step (csrc/spd_solve.hip; the reference calls  */
+/* torch.linalg.solve in kaolin/physics/common/optimization.py): a blocked     */
+/* Cholesky factorisation A = L L^T of a symmetric positive definite float32   */
+/* matrix and the two substitutions for one right-hand side.  No atomics: the  */
+/* same bits on every call; no host read: capturable.                          */
+/* 1 <= n <= kamd_spd_max_n() (1536 = 12 * 128), panels of kamd_spd_panel()    */
+/* columns.  A, L (n, n) row-major; only the lower triangle of A is read and   */
+/* A is not modified; L is lower triangular with exact zeros above the         */
+/* diagonal.  b, x (n).  info: int32[1] on the device, 0 on success, else the  */
+/* 1-based index of the first column whose pivot is <= 0 or not finite (LAPACK */
+/* potrf's convention); L and x are then unspecified, every later launch of    */
+/* the call returns at once, nothing faults and nothing is read back.          */
+/* workspace: kamd_spd_workspace(n) bytes (0: n out of range), 16-byte         */
+/* aligned, not initialised.  kamd_spd_solve_f32 takes the workspace and the   */
+/* info that kamd_spd_factor_f32 filled for this L (it keeps the inverses of   */
+/* the diagonal blocks there).                                                 */
+/* ------------------------------------------------------------------------- */
+int kamd_spd_panel(void);
+int kamd_spd_max_n(void);
+size_t kamd_spd_workspace(int64_t n);
+int kamd_spd_factor_f32(void* stream, int64_t n, const float* A, float* L, int* info, void* workspace);
+int kamd_spd_solve_f32(void* stream, int64_t n, const float* L, const float* b, float* x, const int* info, void* workspace);
+
+/* ------------------------------------------------------------------------- */
 /* Optional per-kernel timing (HIP events recorded on the launch stream).      */
 /* Not part of the reference's interface: used by bench.py for its roofline    */
 /* line; off by default.  kamd_profile_read synchronises the pending events.  */

@@ -1,4 +1,4 @@
-"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip, csrc/skinning_mlp_backward.hip, csrc/simplicits_loss.hip, csrc/collisions.hip and csrc/scene_forces.hip (no reference operator: the reference runs NVIDIA Warp kernels and a dense torch reduction).
+"""Host shims of csrc/physics.hip, csrc/skinning_mlp.hip, csrc/skinning_mlp_backward.hip, csrc/simplicits_loss.hip, csrc/collisions.hip, csrc/scene_forces.hip and csrc/spd_solve.hip (no reference operator: the reference runs NVIDIA Warp kernels, a dense torch reduction and torch.linalg.solve).
 Every argument is a contiguous float32 (indices: int32) tensor on one GPU; shapes are checked by the public layer, kaolin_amd/physics."""
 import ctypes
 
@@ -413,3 +413,49 @@ def scene_reduced_cuda(z, x0, weights, gravity=None, gravity_coeff=0.0, floor=No
             _lib.stream_ptr(dev), N, P, H, _lib.ptr(z), _lib.ptr(x0), _lib.ptr(weights), *gargs, float(gravity_coeff), *fargs,
             float(floor_coeff), *pargs, *iargs, int(bool(hessian)), _lib.ptr(E), _lib.ptr(g), _lib.ptr(K), _lib.ptr(ws), nbytes), fn)
     return E, g, K
+
+
+# ---- csrc/spd_solve.hip -----------------------------------------------------------------------------------------------------------------
+def spd_panel():
+    """Columns of one panel (= the tile side) of the blocked Cholesky factorisation"""
+    return int(_lib.load().kamd_spd_panel())
+
+
+def spd_max_n():
+    """The most rows spd_factor_cuda takes: 12 max_handles()"""
+    return int(_lib.load().kamd_spd_max_n())
+
+
+def spd_factor_cuda(A):
+    """A (n, n) symmetric positive definite, 1 <= n <= spd_max_n(); only its lower triangle is read -> (L (n, n) lower triangular
+    with A = L L^T, info (1) int32: 0 or the 1-based column of the first pivot that is <= 0 or not finite, the workspace that
+    spd_solve_cuda takes).  No host read."""
+    fn = 'spd_factor_cuda'
+    dev = _f32_cuda(fn, A=A)
+    n = A.size(0)
+    torch_check(tuple(A.shape) == (n, n) and 1 <= n <= spd_max_n(), f'{fn}: A must be of size {{n, n}}, n in 1 to {spd_max_n()}')
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        L = torch.empty((n, n), dtype=torch.float32, device=dev)
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _lib.workspace(lib.kamd_spd_workspace(n), dev)
+        _lib.check(lib.kamd_spd_factor_f32(_lib.stream_ptr(dev), n, _lib.ptr(A), _lib.ptr(L), _lib.ptr(info), _lib.ptr(ws)), fn)
+    return L, info, ws
+
+
+def spd_solve_cuda(L, b, info, workspace):
+    """L, info, workspace of spd_factor_cuda, b (n) -> x (n) with L L^T x = b (unspecified where info != 0).  No host read."""
+    fn = 'spd_solve_cuda'
+    dev = _f32_cuda(fn, L=L, b=b)
+    n = L.size(0)
+    lib = _lib.load()
+    torch_check(tuple(L.shape) == (n, n) and 1 <= n <= spd_max_n() and tuple(b.shape) == (n,),
+                f'{fn}: L must be of size {{n, n}}, n in 1 to {spd_max_n()}, and b of size {{n}}')
+    torch_check(info.device == dev and info.dtype == torch.int32 and info.numel() == 1 and workspace is not None and
+                workspace.device == dev and workspace.numel() * 8 >= lib.kamd_spd_workspace(n),
+                f'{fn}: needs the info and the workspace that spd_factor_cuda returned for this L')
+    with _lib.on_device(dev):
+        x = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.kamd_spd_solve_f32(_lib.stream_ptr(dev), n, _lib.ptr(L), _lib.ptr(b), _lib.ptr(x), _lib.ptr(info),
+                                          _lib.ptr(workspace)), fn)
+    return x

@@ -218,6 +218,11 @@ SIGNATURES.update({
     'kamd_scene_reduced_workspace': (_sz, [_i64, _i, _i]),
     'kamd_scene_reduced_f32': (_i, [_vp, _i64, _i64, _i] + [_vp] * 5 + [_f] * 4 + [_vp, _f, _i, _i, _f] + [_vp] * 6 + [_f, _i] +
                                [_vp] * 4 + [_sz]),
+    'kamd_spd_panel': (_i, []),
+    'kamd_spd_max_n': (_i, []),
+    'kamd_spd_workspace': (_sz, [_i64]),
+    'kamd_spd_factor_f32': (_i, [_vp, _i64] + [_vp] * 4),
+    'kamd_spd_solve_f32': (_i, [_vp, _i64] + [_vp] * 5),
 })
 for _t in ('f16', 'f32', 'f64'):
     SIGNATURES[f'kamd_spc_bf_query_{_t}'] = (_i, [_vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp])

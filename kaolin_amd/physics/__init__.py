@@ -5,8 +5,10 @@ their reduced form (kaolin_amd/csrc/collisions.hip), the training of that networ
 kaolin/physics/simplicits/losses.py with their gradient (kaolin_amd/csrc/simplicits_loss.hip) and the network's reverse pass
 (kaolin_amd/csrc/skinning_mlp_backward.hip), and the scene forces: gravity, a floor, pinned points and the inertia term of a
 Newton step, per point and in reduced form (kaolin_amd/csrc/scene_forces.hip).  With these every term of the Newton objective
-has a matrix-free reduced (E, g, K).  SimplicitsScene, the Newton driver and its linear solve, SimplicitsObject and its
-create_with_mlp driver, and a linear elastic material class are not here."""
-from . import collisions, materials, scene_forces, simplicits  # noqa: F401
+has a matrix-free reduced (E, g, K), and optimization takes the step: Newton's method with the reference's line search on a
+Cholesky factorisation and solve of the reduced Hessian (kaolin_amd/csrc/spd_solve.hip).  SimplicitsScene, the conjugate-gradient
+solve, SimplicitsObject and its create_with_mlp driver, and a linear elastic material class are not here."""
+from . import collisions, materials, optimization, scene_forces, simplicits  # noqa: F401
 from .collisions import Collision  # noqa: F401
+from .optimization import cholesky_spd, newtons_method, solve_spd  # noqa: F401
 from .scene_forces import Boundary, Floor, Gravity, lbs_matrix, reduced_scene_terms  # noqa: F401
